@@ -11,7 +11,15 @@ xGMI), every rank vocodes its shard, and rank 0 gathers the waveforms (weak scal
 utterances at N=8).  The compute-only step (each rank on its resident shard) and the scatter /
 gather times are reported beside it.
 
-Prints ONE JSON line (rank 0) with the driver contract fields plus:
+A plain run (``--gpus 1 --steps K --warmup W``) sets up, runs W untimed and K timed steps, writes
+the last timed step's output if ``--dump-outputs DIR`` is given, and prints ONE JSON line (rank 0)
+with the driver contract fields (``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype``,
+``ms_per_step``), the workload description and the provenance of the loaded library (``build``:
+source hash stamped at build time, .so sha256).  The inputs and weights are seeded, so two runs
+with the same arguments vocode the same batch and their dumps can be compared array for array.
+
+``--full`` adds the side measurements to that line (each takes GPU or CPU runs of its own, minutes
+in all; the ``--no-*`` options drop single legs of it):
   roofline     : the dominant kernel family's executed MFMA FLOP/s (the products its algorithm
                  issues: Winograd F(4,4) point products, x3 fp16 products per fp32 MAC in f16x3),
                  timed by a hipEvent pair per launch inside one profiled forward on the stream the
@@ -20,7 +28,9 @@ Prints ONE JSON line (rank 0) with the driver contract fields plus:
   cpu_baseline : the CPU oracle (oracle/hifigan_ref.py, torch.nn.functional fp32, the same
                  ATen kernels as the reference) on the bench's whole [32,80,1024] mel batch
                  (median of 3 runs after one warm-up), rank 0 at N=1 only
-  build        : provenance of the loaded library (source hash stamped at build time, .so sha256)
+  and the other math mode, the accuracy against the fp64 oracle, and the Glow-TTS, XTTS, VITS and
+  ResBlock2 side lines.
+The multi-rank legs are chosen by ``--gpus N`` / ``--rehearse-sharded`` alone.
 """
 from __future__ import annotations
 
@@ -77,6 +87,12 @@ def parse():
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--batch", type=int, default=32, help="utterances per GPU")
     p.add_argument("--frames", type=int, default=1024)
+    p.add_argument("--full", action="store_true",
+                   help="also run the side measurements (profiled forward / roofline, other math mode, accuracy, "
+                        "CPU baselines, Glow-TTS / XTTS / VITS / ResBlock2 lines); the --no-* options trim them")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="write the waveform batch of the last timed step to DIR/waveform.npy (float32; a fixed "
+                        "seeded sample of it above 64 MB)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline time budget")
     p.add_argument("--math-mode", default="f16x3", choices=sorted(MODE_PEAK),
@@ -107,7 +123,10 @@ def parse():
     p.add_argument("--stub", action="store_true",
                    help="TEST ONLY: CPU stand-in vocoder over gloo (exercises the launcher and sharding "
                         "path without a GPU; its numbers are not a measurement)")
-    return p.parse_args()
+    a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 def free_port() -> int:
@@ -271,8 +290,34 @@ def timed(fn, steps, warmup, dev, world):
     return float(t.item()) / steps * 1e3
 
 
-def time_steps(g, mel, steps, warmup, dev, world):
-    return timed(lambda: g.inference(mel), steps, warmup, dev, world)
+def time_steps(g, mel, steps, warmup, dev, world, last=None):
+    """``last``: a list that receives the waveform of the last timed step (--dump-outputs)."""
+    if last is None:
+        return timed(lambda: g.inference(mel), steps, warmup, dev, world)
+
+    def step():
+        last[:] = [g.inference(mel)]
+
+    return timed(step, steps, warmup, dev, world)
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as <out_dir>/<name>.npy in float32.  Arrays that fit the 64 MB
+    budget are written whole; a larger one as the elements at fixed seeded flat indices (sorted,
+    the same for every run of the same shape), so dumps of two builds still compare 1:1."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    room = DUMP_BUDGET_BYTES // (4 * len(arrays))  # elements per array
+    for name, t in arrays.items():
+        x = t.detach().to("cpu", torch.float32).contiguous()
+        if x.numel() > room:
+            idx = torch.randint(x.numel(), (room,), generator=torch.Generator().manual_seed(0)).sort().values
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), x.numpy())
 
 
 class StubVocoder:
@@ -734,10 +779,11 @@ def rank_devices(world, rank, local, dev):
     return out
 
 
-def sharded_step_bench(g, B, T, dev, world, rank, steps, warmup):
+def sharded_step_bench(g, B, T, dev, world, rank, steps, warmup, last=None):
     """Config 4: rank 0 holds [B*world, 80, T] in HBM; one step = scatter the mel shards ->
     every rank vocodes B utterances -> gather the waveforms on rank 0.  Also times the scatter
-    and the gather alone."""
+    and the gather alone.  ``last``: a list that receives rank 0's gathered waveforms of the last
+    timed step (--dump-outputs)."""
     from tts_amd import synthetic
     from tts_amd.sharding import gather_batch, scatter_batch
 
@@ -753,6 +799,8 @@ def sharded_step_bench(g, B, T, dev, world, rank, steps, warmup):
         gather_batch(g.inference(x), n, out=wav_full)
 
     ms = timed(step, steps, warmup, dev, world)
+    if last is not None and rank == 0:
+        last[:] = [wav_full.clone()]  # the collective timings below write into wav_full again
     scatter_ms = timed(lambda: scatter_batch(full, n, (80, T), dev, out=shard), max(3, steps), 1, dev, world)
     gather_ms = timed(lambda: gather_batch(wav, n, out=wav_full), max(3, steps), 1, dev, world)
     # parity of the sharded path: rank 0's gathered rows equal each shard vocoded alone (the
@@ -815,11 +863,15 @@ def main():
     mel = synthetic.mel(B, T, seed=rank).to(dev)  # this rank's resident shard
     g.reserve(B, T)
     sync(dev)
-    compute_ms = time_steps(g, mel, a.steps, a.warmup, dev, world)
+    last = [] if a.dump_outputs else None  # the headline step's output: the sharded step's at N > 1
+    compute_ms = time_steps(g, mel, a.steps, a.warmup, dev, world, last=last if world == 1 else None)
     shard = None
     if dist_on:
-        shard = sharded_step_bench(g, B, T, dev, world, rank, a.steps, a.warmup)
+        shard = sharded_step_bench(g, B, T, dev, world, rank, a.steps, a.warmup, last=last if world > 1 else None)
     ms_per_step = shard["ms"] if world > 1 else compute_ms
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"waveform": last[0]})
+        del last[:]
     value = world * samples_per_step / (ms_per_step / 1e3)
     rtf = (ms_per_step / 1e3) / (world * samples_per_step / SAMPLE_RATE)
 
@@ -880,6 +932,22 @@ def main():
     from tts_amd import _native
 
     rec["build"] = _native.build_info()
+    if rank == 0:
+        progress(f"timed steps done: {ms_per_step:.2f} ms/step")
+    if a.full:
+        side_measurements(a, g, mel, dev, world, rank, compute_ms, rec)
+    if rank == 0:
+        emit(rec)
+    if dist_on:
+        dist.barrier()
+        dist.destroy_process_group()
+    faulthandler.cancel_dump_traceback_later()
+
+
+def side_measurements(a, g, mel, dev, world, rank, compute_ms, rec):
+    """--full: everything the result line reports beyond the timed steps, added to ``rec`` on rank 0."""
+    B, T, pad = a.batch, a.frames, g.inference_padding
+    samples_per_step = B * g.hop_length * (T + 2 * pad)  # per GPU
 
     # dominant-kernel roofline from one profiled forward (hipEvents per launch)
     _, rows = g.profile(mel)
@@ -937,8 +1005,6 @@ def main():
 
     cpu = None
     acc = None
-    if rank == 0:
-        progress(f"timed steps done: {ms_per_step:.2f} ms/step")
     if rank == 0 and world == 1 and not a.no_cpu_baseline:
         acc = accuracy_check(gens, dev)
         cpu = cpu_baseline(mel, a.cpu_utts, pad)
@@ -1004,11 +1070,6 @@ def main():
             "resblock2_decoder": rb2,
             "accuracy_vs_fp64_oracle": acc,
         })
-        emit(rec)
-    if dist_on:
-        dist.barrier()
-        dist.destroy_process_group()
-    faulthandler.cancel_dump_traceback_later()
 
 
 if __name__ == "__main__":

@@ -9,6 +9,7 @@ if [ -z "$AB_NOTEST" ]; then
   timeout -k 10 300 python -m pytest -x -q --timeout 120 --timeout-method thread tests/test_hifigan_gpu.py -m gpu -p no:cacheprovider > gpurun_out/ab_pytest.log 2>&1 || { tail -20 gpurun_out/ab_pytest.log; exit 1; }
   tail -1 gpurun_out/ab_pytest.log
 fi
+AB_BENCH_ARGS="--full $AB_BENCH_ARGS"  # kernel_breakdown_ms comes from --full's profiled forward
 for r in 1 2; do
   for v in $AB; do
     name=${v%%:*}; rest=${v#*:}; lib=${rest%%|*}; envs=${rest#*|}; [ "$envs" = "$rest" ] && envs=""

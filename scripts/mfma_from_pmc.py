@@ -3,7 +3,7 @@
 
 Input: the directory written by scripts/profile_round.sh: a kernel trace (durations) and the
 `sq` PMC pass (SQ_VALU_MFMA_BUSY_CYCLES, GRBM_GUI_ACTIVE, SQ_BUSY_CYCLES, ...) over
-`bench.py --steps S --warmup W`, plus forward_names.json (the launch sequence of one forward).
+`bench.py --full --steps S --warmup W`, plus forward_names.json (the launch sequence of one forward).
 
 Counter handling (MI355X_MICROARCH.md): SQ_VALU_MFMA_BUSY_CYCLES counts MFMA pipe cycles summed
 over every SIMD (32 per v_mfma_f32_32x32x16_{f16,bf16}); GRBM_GUI_ACTIVE is summed over the 8 XCDs,

@@ -2,7 +2,7 @@
 """HBM traffic per launch family of the HiFiGAN-v1 forward, from rocprofv3 PMC passes.
 
 Input: the directory written by scripts/profile_round.sh (a kernel trace, a FETCH_SIZE pass and
-a WRITE_SIZE pass over `bench.py --steps S --warmup W --no-alt --no-glow --no-cpu-baseline`).
+a WRITE_SIZE pass over `bench.py --full --steps S --warmup W --no-alt --no-glow --no-cpu-baseline`).
 Every forward enqueues the same launch sequence (HifiganGenerator executor order), so the
 library's dispatches are cut into forwards and named by position; the names come from the
 profiled forward bench.py dumps (TTS_FORWARD_NAMES=<root>/forward_names.json).
@@ -12,7 +12,7 @@ KiB counters, collected in separate passes.  The gfx950 FETCH_SIZE undercount is
 16-B/lane streaming reads only; our activations stream with 4-B/lane buffer loads, so the FETCH
 scale is calibrated in-run on `amax_mel`, which reads exactly B*80*T fp32 once (f16x3 mode).
 Output: JSON with per_launch_bytes["<mode>:<family>"] and the per-forward total, used by
-bench.py for roofline.traffic and the step-level HBM fraction.
+`bench.py --full` for roofline.traffic and the step-level HBM fraction.
 """
 import csv
 import json

@@ -37,12 +37,22 @@ def tol(mode: str, op: bool = False) -> dict:
 
 
 def goldens(kind: str):
+    """(name, meta, arrays) of every fixture of ``kind``.  A fixture too large for one committed file
+    is <name>.npz (with ``meta``) plus <name>.part<k>.npz holding the rest of its arrays
+    (make_goldens.py save_golden)."""
     out = []
     for p in sorted(glob.glob(os.path.join(GOLDEN, "*.npz"))):
+        if ".part" in os.path.basename(p):
+            continue
         with np.load(p, allow_pickle=False) as z:
             meta = json.loads(str(z["meta"]))
-            if meta["kind"] == kind:
-                out.append((os.path.basename(p)[:-4], meta, {k: z[k] for k in z.files if k != "meta"}))
+            if meta["kind"] != kind:
+                continue
+            arrays = {k: z[k] for k in z.files if k != "meta"}
+        for q in sorted(glob.glob(p[:-4] + ".part*.npz")):
+            with np.load(q, allow_pickle=False) as z:
+                arrays.update({k: z[k] for k in z.files})
+        out.append((os.path.basename(p)[:-4], meta, arrays))
     return out
 
 

@@ -64,6 +64,25 @@ def test_bench_single_rank_has_no_collectives():
     assert rec["n_gpus"] == 1 and "sharded" not in rec and "config5_sharded" not in rec
 
 
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs writes the last timed step's waveforms as float32; the inputs are seeded, so two
+    runs with the same arguments write the same array."""
+    import numpy as np
+
+    outs = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, BENCH, "--stub", "--steps", "3", "--warmup", "1", "--batch", "2",
+                            "--frames", "8", "--dump-outputs", str(tmp_path / d)], env=_env(),
+                           capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr[-3000:]
+        rec = _json_line(r.stdout)
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0
+        assert os.listdir(tmp_path / d) == ["waveform.npy"]
+        outs.append(np.load(tmp_path / d / "waveform.npy"))
+    assert outs[0].dtype == np.float32 and outs[0].shape == (2, 1, 256 * (8 + 10))
+    assert np.abs(outs[0]).max() > 0 and np.array_equal(outs[0], outs[1])
+
+
 def test_bench_rehearse_sharded_single_rank():
     """--rehearse-sharded at N = 1: both sharded legs over a one-rank group, reported beside (not
     instead of) the headline value."""
