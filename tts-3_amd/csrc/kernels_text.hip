@@ -541,6 +541,8 @@ __global__ void __launch_bounds__(256) expand_kernel(ExpandArgs a) {
 void launch_expand(const ExpandArgs& a, int B, hipStream_t s) {
   TTS_REQUIRE(a.T_x <= EXPAND_MAX_TX, 3, "expand: more than " + std::to_string(EXPAND_MAX_TX) + " tokens");
   dim3 grid(ceil_div(a.T_y, 256), B);
+  // at EXPAND_MAX_TX: 64 KiB of dynamic LDS beside the 1 KiB of static partials; the runtime takes the
+  // launch without a raised dynamic-LDS limit (tests/test_text_long_gpu.py runs that token count)
   hipLaunchKernelGGL(expand_kernel, grid, dim3(256), sizeof(float) * (size_t)a.T_x, s, a);
   TTS_HIP_CHECK(hipGetLastError());
 }

@@ -371,8 +371,8 @@ void launch_add_vec_mask(const float* x, const float* v1, const float* v2, const
 }
 
 // out = a + b elementwise (n floats): the SDP's cond(g) + cond_lang(lang_emb) per-utterance vector
-__global__ void __launch_bounds__(256) vec_add_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                      float* __restrict__ out, int n) {
+// (out may alias a: the SDP accumulates in place, so neither carries __restrict__)
+__global__ void __launch_bounds__(256) vec_add_kernel(const float* a, const float* __restrict__ b, float* out, int n) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) out[i] = a[i] + b[i];
 }
