@@ -434,6 +434,46 @@ int tts_vits_posterior_forward_profiled(void* handle, const float* d_x, const fl
                                         int max_records, int* n_records);
 
 /* ------------------------------------------------------------------------------------ */
+/* Linear spectrogram of a waveform: wav_to_spec (TTS/tts/models/vits.py), the posterior   */
+/* encoder's input in voice conversion                                                    */
+/* ------------------------------------------------------------------------------------ */
+
+/* spec = sqrt(|STFT(y)|^2 + 1e-6) as VITS computes it (center=False): with p = (n_fft - hop) / 2
+ * the wav y[B][N] is reflect-padded by p samples on both sides (the edge sample is not repeated:
+ * y[-i] = y[i], y[N-1+i] = y[N-1-i]; needs N > p), framed every hop_length samples
+ * (T = 1 + (N + 2p - n_fft) / hop_length frames, trailing samples that do not fill a frame are
+ * dropped), multiplied by the window (win_length values, zero-padded to n_fft, centred: left pad
+ * (n_fft - win_length) / 2) and transformed: X[k][t] = sum_n window[n] ypad[t hop + n]
+ * e^(-2 pi i k n / n_fft), k = 0 .. n_fft/2.
+ *
+ * One launch (two with the input's max-abs pass in TTS_MATH_FP32_F16X3): a GEMM of the windowed DFT
+ * matrix (packed once per plan) with the frames, on the matrix cores, magnitude fused.
+ * Supported: n_fft a multiple of 32 in [64, 2048]; 1 <= win_length <= n_fft; hop_length a multiple
+ * of 8 in [8, n_fft]; math_mode TTS_MATH_FP32_X6, _F16X3 or TTS_MATH_BF16 (TTS_MATH_FP32 has no
+ * kernel here: TTS_ERR_UNSUPPORTED); N > p and N + 2p >= n_fft; N * 4 and
+ * (n_fft/2 + 1) * T * 4 below 2 GiB.  Outside: TTS_ERR_UNSUPPORTED / TTS_ERR_INVALID. */
+typedef struct TtsStftCfg {
+  int n_fft;      /* 1024 (VITS fft_size) */
+  int hop_length; /* 256 */
+  int win_length; /* 1024 */
+  int math_mode;  /* TTS_MATH_FP32_X6, TTS_MATH_FP32_F16X3 or TTS_MATH_BF16 */
+} TtsStftCfg;
+
+/* h_window: win_length fp32 values on the host (torch.hann_window(win_length) for VITS); the packed
+ * DFT matrix lives in the handle. */
+int tts_stft_create(const TtsStftCfg* cfg, const float* h_window, int device, void** handle);
+int tts_stft_destroy(void* handle);
+/* Frames T of an N-sample wav (host only); -TTS_ERR_* on a bad configuration or N. */
+int tts_stft_num_frames(const TtsStftCfg* cfg, int64_t N);
+/* d_spec[B][n_fft/2 + 1][T] fp32 (T = tts_stft_num_frames(cfg, N)) from d_wav: B rows of N fp32
+ * samples, wav_bstride floats apart (0 = N). */
+int tts_stft_forward(void* handle, const float* d_wav, int B, int64_t N, int64_t wav_bstride, float* d_spec,
+                     void* hip_stream);
+int tts_stft_forward_profiled(void* handle, const float* d_wav, int B, int64_t N, int64_t wav_bstride,
+                              float* d_spec, void* hip_stream, TtsLaunchRecord* records, int max_records,
+                              int* n_records);
+
+/* ------------------------------------------------------------------------------------ */
 /* VITS text side of Vits.inference (TTS/tts/models/vits.py:1121-1155), since ABI 114       */
 /* ------------------------------------------------------------------------------------ */
 

@@ -11,6 +11,7 @@
 #include "glow.hpp"
 #include "handoff.hpp"
 #include "hifigan.hpp"
+#include "stft.hpp"
 #include "text.hpp"
 #include "vits.hpp"
 #include "tts_mi355x.h"
@@ -741,6 +742,53 @@ int tts_vits_posterior_forward_profiled(void* handle, const float* d_x, const fl
     {
       tts::DeviceGuard g(h->device());
       h->forward(d_x, d_mask, d_g, d_eps, B, C, T, d_z, d_m, d_logs, s, &prof);
+      TTS_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    export_records(prof, records, max_records, n_records);
+  });
+}
+
+// ----------------------------------------------------------------------------- linear spectrogram
+int tts_stft_create(const TtsStftCfg* cfg, const float* h_window, int device, void** handle) {
+  return guarded([&] {
+    TTS_REQUIRE(cfg && h_window && handle, 1, "NULL argument");
+    *handle = nullptr;
+    *handle = new tts::Stft(*cfg, h_window, device);
+  });
+}
+
+int tts_stft_destroy(void* handle) {
+  return guarded([&] { delete static_cast<tts::Stft*>(handle); });
+}
+
+int tts_stft_num_frames(const TtsStftCfg* cfg, int64_t N) {
+  int n = -1;
+  int st = guarded([&] {
+    TTS_REQUIRE(cfg, 1, "NULL cfg");
+    n = tts::stft_num_frames(*cfg, N);
+  });
+  return st == TTS_OK ? n : -st;
+}
+
+int tts_stft_forward(void* handle, const float* d_wav, int B, int64_t N, int64_t wav_bstride, float* d_spec,
+                     void* hip_stream) {
+  return guarded([&] {
+    TTS_REQUIRE(handle, 1, "NULL handle");
+    static_cast<tts::Stft*>(handle)->forward(d_wav, B, N, wav_bstride, d_spec, static_cast<hipStream_t>(hip_stream));
+  });
+}
+
+int tts_stft_forward_profiled(void* handle, const float* d_wav, int B, int64_t N, int64_t wav_bstride,
+                              float* d_spec, void* hip_stream, TtsLaunchRecord* records, int max_records,
+                              int* n_records) {
+  return guarded([&] {
+    TTS_REQUIRE(handle && n_records, 1, "NULL argument");
+    auto* h = static_cast<tts::Stft*>(handle);
+    auto s = static_cast<hipStream_t>(hip_stream);
+    tts::Profiler prof;
+    {
+      tts::DeviceGuard g(h->device());
+      h->forward(d_wav, B, N, wav_bstride, d_spec, s, &prof);
       TTS_HIP_CHECK(hipStreamSynchronize(s));
     }
     export_records(prof, records, max_records, n_records);

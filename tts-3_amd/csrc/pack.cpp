@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "stft.hpp"
 #include "wino_consts.hpp"
 
 namespace tts {
@@ -196,6 +197,62 @@ int pack_conv1d_wino(int mode, const float* w, int Cout, int Cin, int K, const C
         std::copy_n(wt.data() + ((size_t)o * Cin + g * 16 + ch) * KS, KS, wp.data() + ((size_t)o * Cin + g * 16 + kk) * KS);
       }
   return pack_conv1d_split(mode, wp.data(), Cout, Cin, KS, t, out, /*quad_perm=*/false);
+}
+
+// ---- windowed DFT matrix of the linear-spectrogram GEMM (layout: stft.hpp) ----
+int stft_pieces(int mode) { return split_pieces(mode); }
+
+int64_t packed_stft_numel16(int mode, int n_fft) {
+  return (int64_t)stft_blocks(n_fft) * (n_fft / 16) * 2 * split_pieces(mode) * 512;
+}
+
+double stft_matrix_entry(const float* window, int win_length, int n_fft, int c, int row, int n) {
+  const int left = (n_fft - win_length) / 2;
+  if (n < left || n >= left + win_length) return 0.0;
+  const double w = (double)window[n - left];
+  if (row == 0 && c == 1) return (n & 1) ? -w : w;  // the Nyquist bin in the DC bin's im slot
+  if (row >= n_fft / 2) return 0.0;
+  // the angle from (k n) mod n_fft: exact integer reduction, so large k n loses nothing
+  const double ang = 2.0 * M_PI * (double)(((int64_t)row * n) % n_fft) / (double)n_fft;
+  return c == 0 ? w * std::cos(ang) : -w * std::sin(ang);
+}
+
+int pack_stft_matrix(int mode, const float* window, int win_length, int n_fft, uint16_t* out) {
+  const int NP = split_pieces(mode);
+  const int nblk = stft_blocks(n_fft), nsteps = n_fft / 16;
+  int e = 0;
+  if (mode == MATH_FP32_F16X3) {
+    float m = 0.f;
+    bool finite = true;
+    for (int i = 0; i < win_length; ++i) {
+      finite = finite && std::isfinite(window[i]);
+      m = std::max(m, std::fabs(window[i]));  // |entry| <= |window|, reached at bin 0
+    }
+    TTS_REQUIRE(finite, 1, "stft window contains inf/NaN");
+    if (m > 0.f) {
+      int E;
+      (void)std::frexp(m, &E);
+      e = E - 14;
+    }
+  }
+  int64_t o = 0;
+  for (int blk = 0; blk < nblk; ++blk)
+    for (int s = 0; s < nsteps; ++s)
+      for (int c = 0; c < 2; ++c) {
+        uint16_t pc[3][64][8];
+        for (int lane = 0; lane < 64; ++lane)
+          for (int j = 0; j < 8; ++j) {
+            const float v = (float)stft_matrix_entry(window, win_length, n_fft, c, blk * 32 + (lane & 31),
+                                                     s * 16 + 8 * (lane >> 5) + j);
+            if (NP == 3) split3_host(v, pc[0][lane][j], pc[1][lane][j], pc[2][lane][j]);
+            else if (NP == 2) split_h3_host(std::ldexp(v, -e), pc[0][lane][j], pc[1][lane][j]);
+            else pc[0][lane][j] = f2bf_rne(v);
+          }
+        for (int p = 0; p < NP; ++p)
+          for (int lane = 0; lane < 64; ++lane)
+            for (int j = 0; j < 8; ++j) out[o++] = pc[p][lane][j];
+      }
+  return e;
 }
 
 }  // namespace tts

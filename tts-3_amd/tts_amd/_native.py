@@ -154,6 +154,15 @@ class TtsVitsPosteriorCfg(Structure):
     ]
 
 
+class TtsStftCfg(Structure):
+    _fields_ = [
+        ("n_fft", c_int),
+        ("hop_length", c_int),
+        ("win_length", c_int),
+        ("math_mode", c_int),
+    ]
+
+
 class TtsVitsTextEncoderCfg(Structure):
     _fields_ = [
         ("n_vocab", c_int),
@@ -300,6 +309,15 @@ SIGNATURES = {
         c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
          c_void_p, POINTER(TtsLaunchRecord), c_int, POINTER(c_int)],
+    ),
+    "tts_stft_create": (c_int, [POINTER(TtsStftCfg), c_void_p, c_int, POINTER(c_void_p)]),
+    "tts_stft_destroy": (c_int, [c_void_p]),
+    "tts_stft_num_frames": (c_int, [POINTER(TtsStftCfg), c_int64]),
+    "tts_stft_forward": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p]),
+    "tts_stft_forward_profiled": (
+        c_int,
+        [c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, POINTER(TtsLaunchRecord), c_int,
+         POINTER(c_int)],
     ),
     "tts_vits_text_encoder_num_weights": (c_int, [POINTER(TtsVitsTextEncoderCfg)]),
     "tts_vits_text_encoder_weight_numel": (c_int64, [POINTER(TtsVitsTextEncoderCfg), c_int]),

@@ -33,7 +33,8 @@ from .. import _native as N
 from ..config import VITS_DECODER, VITS_FLOW, VITS_INFERENCE, VITS_SDP, VITS_TEXT_ENCODER
 from ..vocoder.hifigan_generator import HifiganGenerator
 from .glow_tts import LayerNorm, LayerNorm2, RelativePositionTransformer
-from .vits_flow import ResidualCouplingBlocks
+from .spectrogram import wav_to_spec
+from .vits_flow import PosteriorEncoder, ResidualCouplingBlocks
 
 
 def _f32(t: torch.Tensor) -> np.ndarray:
@@ -565,7 +566,8 @@ def l2_normalize_rows(d: torch.Tensor, dev) -> torch.Tensor:
 
 
 class Vits(nn.Module):
-    """The inference surface of ``TTS/tts/models/vits.py`` (``Vits.inference``, :1088-1174) on MI355X.
+    """The inference surface of ``TTS/tts/models/vits.py`` on MI355X: ``Vits.inference`` (:1088-1174) and
+    voice conversion (``Vits.voice_conversion``, ``Vits.inference_voice_conversion``).
 
     ``args`` takes ``VitsArgs`` field names (vits.py:541-596; unset fields keep the reference
     defaults): num_chars, hidden_channels, the text encoder / flow / decoder / duration predictor
@@ -573,19 +575,27 @@ class Vits(nn.Module):
     use_d_vector_file + d_vector_dim, condition_dp_on_speaker, use_language_embedding +
     num_languages + embedded_language_dim (the reference takes num_languages from its language
     manager, vits.py:796-801), encoder_sample_rate + interpolate_z (with ``sample_rate``, the audio
-    config's rate, vits.py:808-812), length_scale, inference_noise_scale(_dp), max_inference_len.
-    Sub-modules keep the reference names (``text_encoder``, ``duration_predictor``, ``flow``,
-    ``waveform_decoder``, ``emb_g``, ``emb_l``) so a Vits checkpoint's inference keys load unchanged
-    (``load_state_dict(strict=False)`` skips the posterior encoder and discriminator)."""
+    config's rate, vits.py:808-812), length_scale, inference_noise_scale(_dp), max_inference_len, the
+    posterior encoder fields (out_channels, kernel_size / dilation_rate / num_layers_posterior_encoder)
+    and, for voice conversion, the audio fields the reference reads from ``config.audio``: fft_size,
+    hop_length, win_length.
+    Sub-modules keep the reference names (``text_encoder``, ``posterior_encoder``, ``duration_predictor``,
+    ``flow``, ``waveform_decoder``, ``emb_g``, ``emb_l``) so a Vits checkpoint's generator keys, the
+    ``posterior_encoder.*`` ones included, load unchanged (``load_state_dict(strict=False)`` skips the
+    discriminator).  The posterior encoder holds parameters only until voice conversion first runs it:
+    ``inference`` never creates its native handle."""
 
     def __init__(self, args: Optional[Dict] = None, text_math_mode: str = "fp32x6",
-                 flow_math_mode: Optional[str] = None, decoder_math_mode: Optional[str] = None):
+                 flow_math_mode: Optional[str] = None, decoder_math_mode: Optional[str] = None,
+                 posterior_math_mode: Optional[str] = None):
         super().__init__()
         a = dict(num_chars=64, hidden_channels=192, use_sdp=True, use_speaker_embedding=False, num_speakers=0,
                  speaker_embedding_channels=256, use_d_vector_file=False, d_vector_dim=0,
                  condition_dp_on_speaker=True, use_language_embedding=False, num_languages=0,
                  embedded_language_dim=4, encoder_sample_rate=None, interpolate_z=True, sample_rate=22050,
                  max_inference_len=None, dropout_p_duration_predictor=0.5,
+                 out_channels=513, kernel_size_posterior_encoder=5, dilation_rate_posterior_encoder=1,
+                 num_layers_posterior_encoder=16, fft_size=1024, hop_length=256, win_length=1024,
                  num_layers_text_encoder=VITS_TEXT_ENCODER["num_layers"],
                  hidden_channels_ffn_text_encoder=VITS_TEXT_ENCODER["hidden_channels_ffn"],
                  num_heads_text_encoder=VITS_TEXT_ENCODER["num_heads"],
@@ -627,6 +637,10 @@ class Vits(nn.Module):
                                         a["num_heads_text_encoder"], a["num_layers_text_encoder"],
                                         a["kernel_size_text_encoder"], 0.1, language_emb_dim=L,
                                         math_mode=text_math_mode)
+        self.posterior_encoder = PosteriorEncoder(  # vits.py:664-672
+            a["out_channels"], H, H, kernel_size=a["kernel_size_posterior_encoder"],
+            dilation_rate=a["dilation_rate_posterior_encoder"], num_layers=a["num_layers_posterior_encoder"],
+            cond_channels=gin, math_mode=posterior_math_mode)
         self.flow = ResidualCouplingBlocks(H, H, kernel_size=a["kernel_size_flow"], dilation_rate=a["dilation_rate_flow"],
                                            num_layers=a["num_layers_flow"], cond_channels=gin, math_mode=flow_math_mode)
         if a["use_sdp"]:  # vits.py:684-702
@@ -703,3 +717,65 @@ class Vits(nn.Module):
         o = self.waveform_decoder(vits_mask_slice(z, y_mask, self.max_inference_len), g=g)
         return {"model_outputs": o, "alignments": attn, "durations": w_ceil, "z": z, "z_p": z_p, "m_p": m_p,
                 "logs_p": logs_p, "y_mask": y_mask}
+
+    # ------------------------------------------------------------------ voice conversion
+    def _speaker_ids(self, cond) -> torch.Tensor:
+        """Speaker ids [n] int64 on the host, range-checked there (nn.Embedding raises IndexError;
+        embedding_rows would clamp)."""
+        ids = torch.as_tensor(cond).reshape(-1).to(torch.int64).cpu()
+        n = self.args["num_speakers"]
+        bad = [int(i) for i in ids if not 0 <= int(i) < n]
+        if bad:
+            raise IndexError(f"speaker id {bad[0]} is out of range for {n} speakers")
+        return ids
+
+    def _speaker_cond(self, cond, B: int) -> torch.Tensor:
+        """g [B, C, 1] of a speaker id (int, 0-d or 1-d tensor) or a d-vector ([C], [1, C] or [B, C])."""
+        if hasattr(self, "emb_g") and self.args["use_speaker_embedding"]:
+            g = embedding_rows(self.emb_g, self._speaker_ids(cond).to(self._dev()))
+        else:
+            g = l2_normalize_rows(cond, self._dev())  # F.normalize(d)
+        if g.shape[0] == 1 and B > 1:
+            g = g.expand(B, -1)
+        if g.shape[0] != B:
+            raise ValueError(f"speaker conditioning has {g.shape[0]} rows for a batch of {B}")
+        return g.reshape(B, -1, 1).contiguous()
+
+    @torch.no_grad()
+    def voice_conversion(self, y, y_lengths, speaker_cond_src, speaker_cond_tgt, noise=None):
+        """``Vits.voice_conversion`` (vits.py:1198-1232): ``y`` [B, out_channels, T] linear spectrogram,
+        ``y_lengths`` [B], the source and target speakers as ids (``use_speaker_embedding``) or d-vectors
+        (``use_d_vector_file``).  Returns ``(o_hat [B, 1, T * hop], y_mask, (z, z_p, z_hat))``.  ``noise``
+        [B, hidden, T] is a test hook: the posterior's standard-normal draw (drawn on the device when absent)."""
+        a = self.args
+        by_id = bool(a["use_speaker_embedding"] and a["num_speakers"] > 0)
+        if by_id == bool(a["use_d_vector_file"]):
+            raise RuntimeError(" [!] Voice conversion is only supported on multi-speaker models.")
+        if by_id:  # on the host, before anything runs
+            self._speaker_ids(speaker_cond_src)
+            self._speaker_ids(speaker_cond_tgt)
+        if y.device.type != "cuda" or self._dev().type != "cuda":
+            raise RuntimeError("Vits.voice_conversion (tts_amd) runs only on a ROCm device: move the model and the "
+                               "spectrogram with .to('cuda')")
+        B = y.shape[0]
+        g_src = self._speaker_cond(speaker_cond_src, B)
+        g_tgt = self._speaker_cond(speaker_cond_tgt, B)
+        z, _, _, y_mask = self.posterior_encoder(y, y_lengths, g=g_src, noise=noise)
+        z_p = self.flow(z, y_mask, g=g_src)
+        z_hat = self.flow(z_p, y_mask, g=g_tgt, reverse=True)
+        o_hat = self.waveform_decoder(vits_mask_slice(z_hat, y_mask), g=g_tgt)
+        return o_hat, y_mask, (z, z_p, z_hat)
+
+    @torch.no_grad()
+    def inference_voice_conversion(self, reference_wav, speaker_id=None, d_vector=None, reference_speaker_id=None,
+                                   reference_d_vector=None):
+        """``Vits.inference_voice_conversion`` (vits.py:1176-1196): ``reference_wav`` [B, 1, N] or [B, N] on
+        the device, spoken by ``reference_speaker_id`` / ``reference_d_vector``, re-spoken by ``speaker_id`` /
+        ``d_vector``.  Returns the wav [B, 1, T * hop]."""
+        a = self.args
+        y = wav_to_spec(reference_wav, a["fft_size"], a["hop_length"], a["win_length"], center=False)
+        y_lengths = torch.full((y.shape[0],), y.shape[-1], dtype=torch.int64, device=y.device)
+        speaker_cond_src = reference_speaker_id if reference_speaker_id is not None else reference_d_vector
+        speaker_cond_tgt = speaker_id if speaker_id is not None else d_vector
+        wav, _, _ = self.voice_conversion(y, y_lengths, speaker_cond_src, speaker_cond_tgt)
+        return wav
