@@ -21,6 +21,8 @@
  *   Glow-TTS inference glue  TTS/tts/models/glow_tts.py
  *       GlowTTS.inference durations      :349-351   -> tts_glow_durations
  *       generate_path + compute_outputs + z :352-361 -> tts_glow_expand
+ *       GlowTTS.forward / inference_with_MAS logp :218-228 -> tts_glow_mas_logp
+ *       maximum_path (TTS/tts/utils/helpers.py)   -> tts_maximum_path
  *
  * The reference has no native FFI for this path (it is pure Python over ATen); the Python
  * binding a maintainer adds is the ctypes stub in INTEGRATION.md.
@@ -318,6 +320,30 @@ int tts_glow_expand(const float* d_w_ceil, const float* d_x_mask, const int64_t*
                     const float* d_o_mean, const float* d_o_log_scale, const float* d_noise, float noise_scale,
                     int B, int C, int T_x, int T_y, float* d_z, float* d_y_mask, float* d_y_mean,
                     float* d_y_log_scale, float* d_attn, void* hip_stream);
+
+/* The alignment log-likelihood of GlowTTS.forward / inference_with_MAS (glow_tts.py:218-228), with
+ * s = exp(-2 o_log_scale):
+ *   logp[b][x][y] = sum_c(-0.5 log(2 pi) - o_log_scale[c][x]) + sum_c s[c][x] (-0.5 z[c][y]^2)
+ *                 + sum_c (o_mean[c][x] s[c][x]) z[c][y] + sum_c -0.5 o_mean[c][x]^2 s[c][x]
+ * o_mean, o_log_scale [B][C][T_en] (o_log_scale NULL = zeros: mean_only), z [B][C][T_de], logp
+ * [B][T_en][T_de].  One fp32 arithmetic (v_mfma_f32_32x32x2_f32, depth 2C); any C, T_en, T_de >= 1
+ * whose per-item planes stay under 2 GiB. */
+int tts_glow_mas_logp(const float* d_o_mean, const float* d_o_log_scale, const float* d_z, int B, int C, int T_en,
+                      int T_de, float* d_logp, void* hip_stream);
+/* Monotonic Alignment Search (maximum_path): per item the monotonic path through value [T_en][T_de]
+ * (y fastest) from (0, 0) to (t_x - 1, t_y - 1) with the largest sum, found with the reference's
+ * loops (each cell one fp32 max and one fp32 add; ties stay on the token), so the path equals a CPU
+ * evaluation of them exactly.  d_mask (NULL = none) is multiplied into every value on load.  t_x,
+ * t_y [B] int64 on the device.  Outputs, each may be NULL: path [B][T_en][T_de] (0 / 1), durations
+ * [B][T_en] (row sums of the path), log_dur = logf(1 + durations).  Items with t_x < 1, t_y < t_x,
+ * t_x > T_en or t_y > T_de (the reference reads out of bounds there) get an all-zero path and
+ * durations.  d_workspace: tts_maximum_path_workspace_bytes(B, T_en, T_de) bytes of device memory
+ * (never 0; -1 for a shape outside the limits).
+ * Limits: T_en <= 1024, T_en * T_de * 4 bytes < 2 GiB, B <= 65535 (TTS_ERR_UNSUPPORTED beyond). */
+int64_t tts_maximum_path_workspace_bytes(int B, int T_en, int T_de);
+int tts_maximum_path(const float* d_value, const float* d_mask, const int64_t* d_t_x, const int64_t* d_t_y, int B,
+                     int T_en, int T_de, void* d_workspace, float* d_path, float* d_durations, float* d_log_dur,
+                     void* hip_stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* TTS -> vocoder hand-off and the int16 wav writer                                       */

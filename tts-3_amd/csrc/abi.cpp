@@ -11,6 +11,7 @@
 #include "glow.hpp"
 #include "handoff.hpp"
 #include "hifigan.hpp"
+#include "mas.hpp"
 #include "stft.hpp"
 #include "text.hpp"
 #include "vits.hpp"
@@ -244,6 +245,31 @@ int tts_glow_expand(const float* d_w_ceil, const float* d_x_mask, const int64_t*
     a.z = d_z; a.y_mask = d_y_mask; a.y_mean = d_y_mean; a.y_log_scale = d_y_log_scale; a.attn = d_attn;
     tts::launch_expand(a, B, static_cast<hipStream_t>(hip_stream));
     TTS_HIP_CHECK(hipGetLastError());
+  });
+}
+
+int tts_glow_mas_logp(const float* d_o_mean, const float* d_o_log_scale, const float* d_z, int B, int C, int T_en,
+                      int T_de, float* d_logp, void* hip_stream) {
+  return guarded([&] {
+    TTS_REQUIRE(d_o_mean && d_z && d_logp, 1, "NULL argument");
+    TTS_REQUIRE(B >= 1 && C >= 1 && T_en >= 1 && T_de >= 1, 1, "bad logp shape");
+    tts::launch_mas_logp(d_o_mean, d_o_log_scale, d_z, B, C, T_en, T_de, d_logp, static_cast<hipStream_t>(hip_stream));
+  });
+}
+
+int64_t tts_maximum_path_workspace_bytes(int B, int T_en, int T_de) {
+  if (B < 1 || T_en < 1 || T_de < 1 || T_en > tts::MAS_MAX_TEN) return -1;
+  return (int64_t)tts::mas_workspace_bytes(B, T_en, T_de);
+}
+
+int tts_maximum_path(const float* d_value, const float* d_mask, const int64_t* d_t_x, const int64_t* d_t_y, int B,
+                     int T_en, int T_de, void* d_workspace, float* d_path, float* d_durations, float* d_log_dur,
+                     void* hip_stream) {
+  return guarded([&] {
+    TTS_REQUIRE(d_value && d_t_x && d_t_y && d_workspace, 1, "NULL argument");
+    TTS_REQUIRE(B >= 1 && T_en >= 1 && T_de >= 1, 1, "bad maximum_path shape");
+    tts::launch_maximum_path(d_value, d_mask, d_t_x, d_t_y, B, T_en, T_de, d_workspace, d_path, d_durations, d_log_dur,
+                             static_cast<hipStream_t>(hip_stream));
   });
 }
 

@@ -279,6 +279,15 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_int,
          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     ),
+    "tts_glow_mas_logp": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
+    ),
+    "tts_maximum_path_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
+    "tts_maximum_path": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p],
+    ),
     "tts_mel_handoff": (
         c_int,
         [c_void_p, c_int, c_int, c_int, c_int, POINTER(TtsAudioNormCfg), POINTER(TtsAudioNormCfg), c_int, c_float,

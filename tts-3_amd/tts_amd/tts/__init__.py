@@ -1,14 +1,16 @@
 """Acoustic-model surface: the Glow-TTS ``Encoder`` / ``Decoder`` (both directions) /
-``GlowTTS.inference`` / ``GlowTTS.decoder_inference``, and the VITS ``ResidualCouplingBlocks`` flow
+``GlowTTS.inference`` / ``GlowTTS.decoder_inference`` / ``GlowTTS.forward`` / ``GlowTTS.inference_with_MAS``
+with ``maximum_path`` (Monotonic Alignment Search), and the VITS ``ResidualCouplingBlocks`` flow
 (both directions), ``PosteriorEncoder``, the linear spectrogram ``wav_to_spec`` and ``Vits``
 (``inference``, ``voice_conversion``, ``inference_voice_conversion``) with its text side
 (``TextEncoder``, ``StochasticDurationPredictor``), on MI355X."""
 from .glow_decoder import Decoder
 from .glow_tts import Encoder, GlowTTS
+from .helpers import maximum_path
 from .spectrogram import wav_to_spec, wav_to_spec_profile
 from .vits_flow import PosteriorEncoder, ResidualCouplingBlocks
 from .vits_text import DurationPredictor, StochasticDurationPredictor, TextEncoder, Vits
 from .xtts_decoder import HifiDecoder
 
 __all__ = ["Decoder", "DurationPredictor", "Encoder", "GlowTTS", "HifiDecoder", "PosteriorEncoder", "ResidualCouplingBlocks",
-           "StochasticDurationPredictor", "TextEncoder", "Vits", "wav_to_spec", "wav_to_spec_profile"]
+           "StochasticDurationPredictor", "TextEncoder", "Vits", "maximum_path", "wav_to_spec", "wav_to_spec_profile"]

@@ -13,8 +13,9 @@
 
 The nn modules below only hold parameters; the handle is rebuilt when any parameter changes.
 Multi-speaker models (``use_speaker_embedding`` / ``use_d_vector_file``, glow_tts.py:107-191)
-condition the duration predictor and the decoder flows on ``g``.  Training (``forward``, MAS)
-is outside the MI355X path.
+condition the duration predictor and the decoder flows on ``g``.  ``GlowTTS.forward`` (:193-247) and
+``GlowTTS.inference_with_MAS`` (:249-316) align a text with a given mel on the device (log-likelihood
+matrix, Monotonic Alignment Search, expansion), without gradients: training is outside the MI355X path.
 """
 from __future__ import annotations
 
@@ -31,6 +32,7 @@ from torch.nn import functional as F
 from .. import _native as N
 from ..config import GLOW_TTS_DECODER, GLOW_TTS_ENCODER, GLOW_TTS_INFERENCE
 from .glow_decoder import Decoder
+from .helpers import mas_logp, maximum_path_lengths
 
 
 class LayerNorm(nn.Module):
@@ -561,7 +563,8 @@ class GlowTTS(nn.Module):
 
     def _speaker_embedding(self, aux_input: Optional[Dict]) -> Optional[torch.Tensor]:  # glow_tts.py:179-191
         """speaker ids -> F.normalize(emb_g(ids)) or d-vectors -> F.normalize(d): [B, c_in, 1].
-        A few hundred floats: the lookup and the normalisation stay in torch on the device."""
+        A few hundred floats: the lookup stays in torch on the device; d-vectors are normalised by
+        ``tts_l2_normalize_rows``."""
         g = self._set_speaker_input(aux_input)
         if g is None:
             return None
@@ -573,7 +576,11 @@ class GlowTTS(nn.Module):
             if not g.size():
                 g = g.unsqueeze(0)
             return F.normalize(self.emb_g(g)).unsqueeze(-1)
-        return F.normalize(g.to(device=dev, dtype=torch.float32)).unsqueeze(-1)
+        d = g.to(device=dev, dtype=torch.float32)
+        d = d.reshape(d.shape[0] if d.dim() > 1 else 1, -1).contiguous()
+        out = torch.empty_like(d)  # F.normalize(d).unsqueeze(-1)
+        N.call("tts_l2_normalize_rows", N.ptr(d), d.shape[0], d.shape[1], N.ptr(out), N.stream_ptr(dev))
+        return out.unsqueeze(-1)
 
     @torch.no_grad()
     def inference(self, x, aux_input={"x_lengths": None, "d_vectors": None, "speaker_ids": None}):  # noqa: B006
@@ -638,6 +645,84 @@ class GlowTTS(nn.Module):
         z, logdet = self.decoder(y, y_mask, g=g, reverse=False)  # :333
         y, logdet = self.decoder(z, y_mask[:, :, : z.shape[2]], g=g, reverse=True)  # :335
         return {"model_outputs": y.transpose(1, 2), "logdet": logdet}
+
+    def preprocess(self, y, y_lengths, y_max_length, attn=None):  # glow_tts.py:376-385
+        """Trim the frame axis to a multiple of ``num_squeeze``: y [B, C, T] (and attn [B, 1, T_en, T] if
+        given) are cut to ``y_max_length // num_squeeze * num_squeeze`` frames and every length is
+        floored to a multiple of ``num_squeeze``."""
+        if y_max_length is not None:
+            y_max_length = (y_max_length // self.num_squeeze) * self.num_squeeze
+            y = y[:, :, :y_max_length]
+            if attn is not None:
+                attn = attn[:, :, :, :y_max_length]
+        y_lengths = torch.div(y_lengths, self.num_squeeze, rounding_mode="floor") * self.num_squeeze
+        return y, y_lengths, y_max_length, attn
+
+    def _align(self, x, x_lengths, y, y_lengths, aux_input):
+        """The steps forward and inference_with_MAS share (glow_tts.py:206-236 / :262-290): encoder,
+        preprocess, decoder forward, log-likelihood matrix, Monotonic Alignment Search and the expansion
+        of the encoder outputs along the path, all on the device and without a host copy."""
+        dev = self._device()
+        y = y.to(device=dev, dtype=torch.float32).transpose(1, 2)
+        B = y.shape[0]
+        g = self._speaker_embedding(aux_input)
+        if self.c_in_channels and g is None:
+            raise ValueError("multi-speaker Glow-TTS: pass aux_input speaker_ids or d_vectors")
+        o_mean, o_log_scale, o_dur_log, x_mask = self.encoder(x, x_lengths, g=g)
+        if y_lengths is None:
+            y_lengths = torch.full((B,), y.shape[2], dtype=torch.int64, device=dev)
+        y_lengths = torch.as_tensor(y_lengths).to(device=dev, dtype=torch.int64).reshape(B)
+        y, y_lengths, T_y, _ = self.preprocess(y, y_lengths, y.shape[2], None)
+        if T_y < 1:
+            raise ValueError(f"y has fewer than num_squeeze = {self.num_squeeze} frames")
+        y_lengths = y_lengths.clamp(max=T_y).contiguous()  # sequence_mask(y_lengths, y_max_length)
+        y_mask = (torch.arange(T_y, device=dev)[None, :] < y_lengths[:, None]).to(torch.float32).unsqueeze(1)
+        z, logdet = self.decoder(y, y_mask, g=g, reverse=False)
+        ls = None if self.mean_only else o_log_scale
+        logp = mas_logp(o_mean, ls, z)
+        # attn_mask = x_mask (x) y_mask (:216) as lengths; the path comes back through its durations
+        t_x = torch.as_tensor(x_lengths).to(device=dev, dtype=torch.int64).reshape(B)
+        _, dur, log_dur = maximum_path_lengths(logp, t_x, y_lengths, want_path=False)
+        # compute_outputs (:138-148) for a hard alignment: the expansion of GlowTTS.inference, no noise
+        C, T_x = o_mean.shape[1], o_mean.shape[2]
+        zm = torch.empty(B, C, T_y, device=dev)  # y_mean * y_mask
+        ym = torch.empty(B, 1, T_y, device=dev)
+        y_mean = torch.empty(B, C, T_y, device=dev)
+        y_log_scale = torch.empty(B, C, T_y, device=dev)
+        attn = torch.empty(B, T_x, T_y, device=dev)
+        N.call("tts_glow_expand", N.ptr(dur), N.ptr(x_mask), N.ptr(y_lengths), N.ptr(o_mean), N.ptr(ls), N.ptr(None),
+               0.0, B, C, T_x, T_y, N.ptr(zm), N.ptr(ym), N.ptr(y_mean), N.ptr(y_log_scale), N.ptr(attn),
+               N.stream_ptr(dev))
+        o_attn_dur = log_dur.unsqueeze(1) * x_mask  # log(1 + sum(attn, -1)) * x_mask (:147)
+        out = {
+            "logdet": logdet,
+            "y_mean": y_mean.transpose(1, 2),
+            "y_log_scale": y_log_scale.transpose(1, 2),
+            "alignments": attn.permute(0, 2, 1),
+            "durations_log": o_dur_log.transpose(1, 2),
+            "total_durations_log": o_attn_dur.transpose(1, 2),
+        }
+        return out, z, zm, y_mask, g
+
+    @torch.no_grad()
+    def forward(self, x, x_lengths, y, y_lengths=None, aux_input={"d_vectors": None, "speaker_ids": None}):  # noqa: B006
+        """glow_tts.py:193-247 without gradients: align the tokens x [B, T_en] with the mel y
+        [B, T_de, C].  Returns z [B, T, C], logdet [B], y_mean, y_log_scale [B, T, C], alignments
+        [B, T, T_en], durations_log, total_durations_log [B, T_en, 1]; T is T_de floored to a multiple
+        of ``num_squeeze``."""
+        out, z, _, _, _ = self._align(x, x_lengths, y, y_lengths, aux_input)
+        return {"z": z.transpose(1, 2), **out}
+
+    @torch.no_grad()
+    def inference_with_MAS(self, x, x_lengths, y=None, y_lengths=None,
+                           aux_input={"d_vectors": None, "speaker_ids": None}):  # noqa: B006
+        """glow_tts.py:249-316: the alignment of ``forward``, then z = y_mean * y_mask decoded back.
+        ``model_outputs`` is that z transposed (what the reference returns) and ``logdet`` the reverse
+        pass's; the decoded mel is under the extra key ``"y"`` [B, T, C]."""
+        out, _, zm, y_mask, g = self._align(x, x_lengths, y, y_lengths, aux_input)
+        y_dec, logdet = self.decoder(zm, y_mask, g=g, reverse=True)
+        out["logdet"] = logdet
+        return {"model_outputs": zm.transpose(1, 2), "y": y_dec.transpose(1, 2), **out}
 
     def store_inverse(self):  # glow_tts.py:519-520
         self.decoder.store_inverse()
