@@ -683,6 +683,73 @@ int tts_op_conv_transpose1d(const float* d_x, int B, int Cin, int Tin, const flo
 int tts_op_conv_post(const float* d_z, int B, int Cin, int T, const float* h_w, const float* h_b,
                      float in_slope, float* d_y, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------ */
+/* MelGAN-family generators: MelGAN, full-band MelGAN, multi-band MelGAN (+ PQMF)          */
+/* ------------------------------------------------------------------------------------ */
+
+/* Mirrors MelganGenerator.__init__ (TTS/vocoder/models/melgan_generator.py): reflection pad +
+ * conv proj_kernel to base_channels; per upsampling i: leaky_relu(0.2), ConvTranspose1d(base >> i,
+ * base >> (i+1), 2u, stride u), ResidualStack(num_res_blocks, res_kernel, dilations res_kernel^j);
+ * leaky_relu(0.2), reflection pad, conv proj_kernel to out_channels, tanh.  pqmf_bands > 0
+ * (= out_channels): the multi-band generator's PQMF synthesis (layers/pqmf.py) for synth = 1.
+ * Implemented: upsample_factors 2, 4 or 8; proj_kernel 3, 5, 7 or 11; res_kernel 3;
+ * num_res_blocks <= 4; base_channels <= 512; out_channels <= 4; pqmf_taps even, <= 126;
+ * math_mode TTS_MATH_FP32_X6 or TTS_MATH_BF16 (TTS_MATH_FP32 and TTS_MATH_FP32_F16X3 run the
+ * fp32x6 kernels: both are held to the fp32 parity gates).  Outside: TTS_ERR_UNSUPPORTED /
+ * TTS_ERR_INVALID. */
+typedef struct TtsMelganCfg {
+  int in_channels;
+  int out_channels;
+  int proj_kernel;
+  int base_channels;
+  int num_ups;
+  int upsample_factors[TTS_MAX_UPSAMPLES];
+  int res_kernel;
+  int num_res_blocks;
+  int pqmf_bands; /* 0 = none */
+  int pqmf_taps;
+  int math_mode;
+} TtsMelganCfg;
+
+/* Host weights: the convs in state_dict order, folded (remove_weight_norm), weight then bias each:
+ *   layers.1.weight [base][in][pk], layers.1.bias
+ *   per upsampling i (C = base >> (i+1)): layers.(3+3i).weight [2C][C][2u], .bias [C]; then its stack:
+ *     blocks.j.2.weight [C][C][rk], .bias, blocks.j.4.weight [C][C][1], .bias for j < num_res_blocks,
+ *     then shortcuts.j.weight [C][C][1], .bias for j < num_res_blocks
+ *   layers.(4+3n).weight [out][base >> n][pk], .bias
+ *   pqmf_layer.G [1][bands][taps+1]  (only if pqmf_bands > 0) */
+int tts_melgan_num_weights(const TtsMelganCfg* cfg);
+int64_t tts_melgan_weight_numel(const TtsMelganCfg* cfg, int idx);
+int tts_melgan_create(const TtsMelganCfg* cfg, const float* const* host_weights, int device, void** handle);
+int tts_melgan_destroy(void* handle);
+/* Samples per batch item and output channel: hop (T + 2 pad), times pqmf_bands when synth.
+ * -TTS_ERR_INVALID when a reflection pad would be >= the plane it pads (as torch refuses it),
+ * -TTS_ERR_UNSUPPORTED beyond the 32-bit plane range; tts_last_error() names the pad. */
+int64_t tts_melgan_output_length(const void* handle, int T, int pad, int synth);
+int64_t tts_melgan_workspace_bytes(const void* handle, int B, int T, int pad);
+/* out = layers(replicate_pad(mel[B][C][T], pad)): [B][out_channels][hop (T + 2 pad)] (synth = 0,
+ * MelganGenerator.forward / the sub-bands) or [B][1][bands hop (T + 2 pad)] (synth = 1: the PQMF
+ * synthesis fused into the last launch; needs pqmf_bands > 0).  pad = 2 is .inference. */
+int tts_melgan_forward(void* handle, const float* d_mel, int B, int C, int T, int pad, int synth, float* d_out,
+                       void* hip_stream);
+int tts_melgan_forward_profiled(void* handle, const float* d_mel, int B, int C, int T, int pad, int synth,
+                                float* d_out, void* hip_stream, TtsLaunchRecord* records, int max_records,
+                                int* n_records);
+
+/* One residual block of a MelGAN ResidualStack (layers/melgan.py), kernel 3:
+ *   d_out = ws x + bs + w2 lrelu(w1 (*)_dilation reflpad(lrelu(x, 0.2)) + b1, 0.2) + b2
+ * x, out [B][C][L] on the device (not aliased); w1 [C][C][3], w2 / ws [C][C][1] and the biases on
+ * the host.  math_mode as TtsMelganCfg.  L > dilation (TTS_ERR_INVALID otherwise). */
+int tts_op_melgan_block(const float* d_x, int B, int C, int L, int dilation, const float* h_w1, const float* h_b1,
+                        const float* h_w2, const float* h_b2, const float* h_ws, const float* h_bs, int math_mode,
+                        float* d_out, void* hip_stream);
+/* Output columns one workgroup of the block kernel computes. */
+int tts_op_melgan_block_tile(void);
+/* d_out[B][1][bands L] = PQMF.synthesis(d_x[B][bands][L]) with d_G [bands][taps+1] on the device
+ * (polyphase form: bands * sum over the taps j with (n + j - taps/2) % bands == 0, zeros outside). */
+int tts_pqmf_synthesis(const float* d_x, int B, int bands, int L, const float* d_G, int taps, float* d_out,
+                       void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@
 #include "handoff.hpp"
 #include "hifigan.hpp"
 #include "mas.hpp"
+#include "melgan.hpp"
 #include "stft.hpp"
 #include "text.hpp"
 #include "vits.hpp"
@@ -956,6 +957,116 @@ int tts_op_conv_post(const float* d_z, int B, int Cin, int T, const float* h_w, 
     auto s = static_cast<hipStream_t>(hip_stream);
     tts::launch_conv_post(a, B, s);
     TTS_HIP_CHECK(hipStreamSynchronize(s));
+  });
+}
+
+// ----------------------------------------------------------------------------- MelGAN family
+int tts_melgan_num_weights(const TtsMelganCfg* cfg) {
+  int n = -1;
+  int st = guarded([&] {
+    TTS_REQUIRE(cfg, 1, "NULL cfg");
+    n = (int)tts::melgan_weight_shapes(*cfg).size();
+  });
+  return st == TTS_OK ? n : -st;
+}
+
+int64_t tts_melgan_weight_numel(const TtsMelganCfg* cfg, int idx) {
+  int64_t n = -1;
+  guarded([&] {
+    TTS_REQUIRE(cfg, 1, "NULL cfg");
+    auto s = tts::melgan_weight_shapes(*cfg);
+    TTS_REQUIRE(idx >= 0 && idx < (int)s.size(), 1, "weight index out of range");
+    n = s[idx];
+  });
+  return n;
+}
+
+int tts_melgan_create(const TtsMelganCfg* cfg, const float* const* host_weights, int device, void** handle) {
+  return guarded([&] {
+    TTS_REQUIRE(cfg && host_weights && handle, 1, "NULL argument");
+    *handle = nullptr;
+    *handle = new tts::Melgan(*cfg, host_weights, device);
+  });
+}
+
+int tts_melgan_destroy(void* handle) {
+  return guarded([&] { delete static_cast<tts::Melgan*>(handle); });
+}
+
+int64_t tts_melgan_output_length(const void* handle, int T, int pad, int synth) {
+  int64_t n = -1;
+  int st = guarded([&] {
+    TTS_REQUIRE(handle, 1, "NULL handle");
+    n = static_cast<const tts::Melgan*>(handle)->out_len(T, pad, synth);
+  });
+  return st == TTS_OK ? n : -st;
+}
+
+int64_t tts_melgan_workspace_bytes(const void* handle, int B, int T, int pad) {
+  int64_t n = -1;
+  int st = guarded([&] {
+    TTS_REQUIRE(handle, 1, "NULL handle");
+    n = static_cast<const tts::Melgan*>(handle)->workspace_bytes(B, T, pad);
+  });
+  return st == TTS_OK ? n : -st;
+}
+
+int tts_melgan_forward(void* handle, const float* d_mel, int B, int C, int T, int pad, int synth, float* d_out,
+                       void* hip_stream) {
+  return guarded([&] {
+    TTS_REQUIRE(handle, 1, "NULL handle");
+    static_cast<tts::Melgan*>(handle)->forward(d_mel, B, C, T, pad, synth, d_out, static_cast<hipStream_t>(hip_stream));
+  });
+}
+
+int tts_melgan_forward_profiled(void* handle, const float* d_mel, int B, int C, int T, int pad, int synth,
+                                float* d_out, void* hip_stream, TtsLaunchRecord* records, int max_records,
+                                int* n_records) {
+  return guarded([&] {
+    TTS_REQUIRE(handle && n_records, 1, "NULL argument");
+    auto* h = static_cast<tts::Melgan*>(handle);
+    auto s = static_cast<hipStream_t>(hip_stream);
+    tts::Profiler prof;
+    {
+      tts::DeviceGuard g(h->device());
+      h->forward(d_mel, B, C, T, pad, synth, d_out, s, &prof);
+      TTS_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    export_records(prof, records, max_records, n_records);
+  });
+}
+
+int tts_op_melgan_block(const float* d_x, int B, int C, int L, int dilation, const float* h_w1, const float* h_b1,
+                        const float* h_w2, const float* h_b2, const float* h_ws, const float* h_bs, int math_mode,
+                        float* d_out, void* hip_stream) {
+  return guarded([&] {
+    TTS_REQUIRE(d_x && h_w1 && h_b1 && h_w2 && h_b2 && h_ws && h_bs && d_out, 1, "NULL argument");
+    TTS_REQUIRE(math_mode >= tts::MATH_FP32 && math_mode <= tts::MATH_LAST, 1, "unknown math_mode");
+    TTS_REQUIRE(B >= 1 && C >= 1 && L >= 1 && dilation >= 1, 1, "bad melgan block shape");
+    const int mode = math_mode == tts::MATH_BF16 ? tts::MATH_BF16 : tts::MATH_FP32_X6;
+    TTS_REQUIRE(C <= tts::kMelganMaxC, 3, "melgan block: channels must lie in [1, 256]");
+    const int64_t n1 = tts::packed_melgan_a1_numel16(mode, C), n2 = tts::packed_melgan_a2_numel16(mode, C);
+    const size_t nb = (size_t)32 * tts::melgan_mblocks(C);
+    std::vector<float> a1((size_t)n1 / 2), a2((size_t)n2 / 2), bias1(nb), bias2(nb);
+    tts::pack_melgan_block(mode, h_w1, h_b1, h_w2, h_b2, h_ws, h_bs, C, reinterpret_cast<uint16_t*>(a1.data()),
+                           reinterpret_cast<uint16_t*>(a2.data()), bias1.data(), bias2.data());
+    TmpDev da1(a1.data(), a1.size()), da2(a2.data(), a2.size()), db1(bias1.data(), nb), db2(bias2.data(), nb);
+    tts::MelganBlockArgs a{};
+    a.x = d_x; a.y = d_out; a.a1 = da1.p; a.a2 = da2.p; a.bias1 = db1.p; a.bias2 = db2.p;
+    a.a1_bytes = (unsigned)(n1 * 2); a.a2_bytes = (unsigned)(n2 * 2);
+    a.C = C; a.L = L; a.dil = dilation;
+    auto s = static_cast<hipStream_t>(hip_stream);
+    tts::launch_melgan_block(mode, a, B, s);
+    TTS_HIP_CHECK(hipStreamSynchronize(s));
+  });
+}
+
+int tts_op_melgan_block_tile(void) { return tts::kMelganBlockTile; }
+
+int tts_pqmf_synthesis(const float* d_x, int B, int bands, int L, const float* d_G, int taps, float* d_out,
+                       void* hip_stream) {
+  return guarded([&] {
+    tts::launch_pqmf_synthesis(d_x, B, bands, L, d_G, taps, d_out, static_cast<hipStream_t>(hip_stream));
   });
 }
 

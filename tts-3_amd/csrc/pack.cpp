@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "melgan.hpp"
 #include "stft.hpp"
 #include "wino_consts.hpp"
 
@@ -253,6 +254,64 @@ int pack_stft_matrix(int mode, const float* window, int win_length, int n_fft, u
             for (int j = 0; j < 8; ++j) out[o++] = pc[p][lane][j];
       }
   return e;
+}
+
+// ---- MelGAN residual block (melgan.hpp): A1 = W1 by (group, tap), A2 = [W2 | Ws], 32-row blocks ----
+int melgan_pieces(int mode) { return split_pieces(mode); }
+
+int64_t packed_melgan_a1_numel16(int mode, int C) {
+  return (int64_t)melgan_mblocks(C) * 3 * melgan_groups(C) * split_pieces(mode) * 512;
+}
+
+int64_t packed_melgan_a2_numel16(int mode, int C) {
+  return (int64_t)melgan_mblocks(C) * 2 * melgan_groups(C) * split_pieces(mode) * 512;
+}
+
+float melgan_a1_entry(const float* w1, int C, int row, int col) {
+  const int s = col / 16, g = s / 3, k = s % 3, ci = 16 * g + col % 16;
+  return (row < C && ci < C) ? w1[((int64_t)row * C + ci) * 3 + k] : 0.f;
+}
+
+float melgan_a2_entry(const float* w2, const float* ws, int C, int row, int col) {
+  const int G = melgan_groups(C), s = col / 16;
+  const int ci = 16 * (s < G ? s : s - G) + col % 16;
+  if (row >= C || ci >= C) return 0.f;
+  return (s < G ? w2 : ws)[(int64_t)row * C + ci];
+}
+
+namespace {
+template <class F>
+void pack_melgan_a(int mode, int MB, int nsteps, uint16_t* out, F&& entry) {
+  const int NP = split_pieces(mode);
+  int64_t o = 0;
+  for (int mb = 0; mb < MB; ++mb)
+    for (int s = 0; s < nsteps; ++s) {
+      uint16_t pc[3][64][8];
+      for (int lane = 0; lane < 64; ++lane)
+        for (int j = 0; j < 8; ++j) {
+          const float v = entry(mb * 32 + (lane & 31), s * 16 + 8 * (lane >> 5) + j);
+          if (NP == 3) split3_host(v, pc[0][lane][j], pc[1][lane][j], pc[2][lane][j]);
+          else pc[0][lane][j] = f2bf_rne(v);
+        }
+      for (int p = 0; p < NP; ++p)
+        for (int lane = 0; lane < 64; ++lane)
+          for (int j = 0; j < 8; ++j) out[o++] = pc[p][lane][j];
+    }
+}
+}  // namespace
+
+void pack_melgan_block(int mode, const float* w1, const float* b1, const float* w2, const float* b2,
+                       const float* ws, const float* bs, int C, uint16_t* a1, uint16_t* a2, float* bias1,
+                       float* bias2) {
+  TTS_REQUIRE(mode == MATH_FP32_X6 || mode == MATH_BF16, 3, "melgan block: math mode must be fp32x6 or bf16");
+  TTS_REQUIRE(C >= 1 && C <= kMelganMaxC, 3, "melgan block: channels must lie in [1, 256]");
+  const int MB = melgan_mblocks(C), G = melgan_groups(C);
+  pack_melgan_a(mode, MB, 3 * G, a1, [&](int row, int col) { return melgan_a1_entry(w1, C, row, col); });
+  pack_melgan_a(mode, MB, 2 * G, a2, [&](int row, int col) { return melgan_a2_entry(w2, ws, C, row, col); });
+  for (int r = 0; r < 32 * MB; ++r) {
+    bias1[r] = r < C ? b1[r] : 0.f;
+    bias2[r] = r < C ? b2[r] + bs[r] : 0.f;
+  }
 }
 
 }  // namespace tts

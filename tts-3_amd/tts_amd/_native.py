@@ -163,6 +163,22 @@ class TtsStftCfg(Structure):
     ]
 
 
+class TtsMelganCfg(Structure):
+    _fields_ = [
+        ("in_channels", c_int),
+        ("out_channels", c_int),
+        ("proj_kernel", c_int),
+        ("base_channels", c_int),
+        ("num_ups", c_int),
+        ("upsample_factors", c_int * MAX_UPSAMPLES),
+        ("res_kernel", c_int),
+        ("num_res_blocks", c_int),
+        ("pqmf_bands", c_int),
+        ("pqmf_taps", c_int),
+        ("math_mode", c_int),
+    ]
+
+
 class TtsVitsTextEncoderCfg(Structure):
     _fields_ = [
         ("n_vocab", c_int),
@@ -395,6 +411,25 @@ SIGNATURES = {
     "tts_op_conv_post": (
         c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p]
     ),
+    "tts_melgan_num_weights": (c_int, [POINTER(TtsMelganCfg)]),
+    "tts_melgan_weight_numel": (c_int64, [POINTER(TtsMelganCfg), c_int]),
+    "tts_melgan_create": (c_int, [POINTER(TtsMelganCfg), POINTER(c_void_p), c_int, POINTER(c_void_p)]),
+    "tts_melgan_destroy": (c_int, [c_void_p]),
+    "tts_melgan_output_length": (c_int64, [c_void_p, c_int, c_int, c_int]),
+    "tts_melgan_workspace_bytes": (c_int64, [c_void_p, c_int, c_int, c_int]),
+    "tts_melgan_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "tts_melgan_forward_profiled": (
+        c_int,
+        [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, POINTER(TtsLaunchRecord), c_int,
+         POINTER(c_int)],
+    ),
+    "tts_op_melgan_block": (
+        c_int,
+        [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+         c_void_p, c_void_p],
+    ),
+    "tts_op_melgan_block_tile": (c_int, []),
+    "tts_pqmf_synthesis": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -24,6 +24,12 @@ HIFIGAN_V1: Dict[str, Any] = {
     "resblock_type": "1",
 }
 
+# MelGAN family: ``generator_model_params`` of MelganConfig (TTS/vocoder/configs/melgan_config.py),
+# MultibandMelganConfig and FullbandMelganConfig (the model zoo's multiband-melgan / fullband-melgan)
+MELGAN: Dict[str, Any] = {"upsample_factors": [8, 8, 2, 2], "num_res_blocks": 3}
+MULTIBAND_MELGAN: Dict[str, Any] = {"upsample_factors": [8, 4, 2], "num_res_blocks": 4}
+FULLBAND_MELGAN: Dict[str, Any] = {"upsample_factors": [8, 8, 2, 2], "num_res_blocks": 4}
+
 GLOW_TTS_DECODER: Dict[str, Any] = {
     "in_channels": 80,          # out_channels
     "hidden_channels": 192,     # hidden_channels_dec

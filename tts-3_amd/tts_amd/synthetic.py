@@ -122,6 +122,67 @@ def hifigan_state_dict(
     return sd
 
 
+def melgan_state_dict(
+    in_channels: int = 80,
+    out_channels: int = 1,
+    proj_kernel: int = 7,
+    base_channels: int = 512,
+    upsample_factors: Sequence[int] = (8, 8, 2, 2),
+    res_kernel: int = 3,
+    num_res_blocks: int = 3,
+    pqmf: bool = False,
+    seed: int = 1234,
+    weight_norm: bool = True,
+    shortcut_scale: float = 0.85,
+    block_scale: float = 0.85,
+    tail_scale: float = None,
+    **_unused,
+) -> "OrderedDict[str, torch.Tensor]":
+    """State dict of a MelganGenerator / FullbandMelganGenerator / MultibandMelganGenerator (``pqmf``:
+    with the ``pqmf_layer`` buffers) with synthetic weights, in the reference's key order.
+
+    The conv scales keep the activations' variance about constant through a residual stack
+    (``shortcut(x) + block(x)`` would otherwise double it per block: the shortcut passes 0.85^2 of the
+    power, and the block's two convs, each behind a leaky_relu(0.2) that passes 0.52, add about 0.14), and the last
+    conv's scale leaves the waveform well inside tanh's range, so parity gates on it mean something.
+    """
+    rng = np.random.default_rng(seed)
+    sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+
+    def put(name: str, w: np.ndarray, cout: int):
+        sd[f"{name}.bias"] = torch.from_numpy((rng.standard_normal((cout,)) * 0.01).astype(np.float32))
+        g, v = _wn_pair(rng, w)
+        if weight_norm:
+            sd[f"{name}.parametrizations.weight.original0"] = torch.from_numpy(g)
+            sd[f"{name}.parametrizations.weight.original1"] = torch.from_numpy(v)
+        else:
+            wf = (g / np.sqrt((v.astype(np.float64) ** 2).sum(axis=(1, 2), keepdims=True))) * v
+            sd[f"{name}.weight"] = torch.from_numpy(np.ascontiguousarray(wf, dtype=np.float32))
+
+    def conv(name: str, cout: int, cin: int, k: int, scale: float):
+        put(name, rng.standard_normal((cout, cin, k)) * (scale / np.sqrt(cin * k)), cout)
+
+    conv("layers.1", base_channels, in_channels, proj_kernel, 0.5)
+    for i, u in enumerate(upsample_factors):
+        cin, c = base_channels >> i, base_channels >> (i + 1)
+        put(f"layers.{3 + 3 * i}", rng.standard_normal((cin, c, 2 * u)) * (1.4 / np.sqrt(2 * cin)), c)
+        for j in range(num_res_blocks):
+            conv(f"layers.{4 + 3 * i}.blocks.{j}.2", c, c, res_kernel, block_scale)
+            conv(f"layers.{4 + 3 * i}.blocks.{j}.4", c, c, 1, block_scale)
+        for j in range(num_res_blocks):
+            conv(f"layers.{4 + 3 * i}.shortcuts.{j}", c, c, 1, shortcut_scale)
+    n = len(upsample_factors)
+    if tail_scale is None:
+        tail_scale = 0.3 if pqmf else 0.8
+    conv(f"layers.{4 + 3 * n}", out_channels, base_channels >> n, proj_kernel, tail_scale)
+    if pqmf:
+        from .vocoder.pqmf import PQMF
+
+        for k, v in PQMF(N=out_channels, taps=62, cutoff=0.15, beta=9.0).state_dict().items():
+            sd[f"pqmf_layer.{k}"] = v.clone()
+    return sd
+
+
 def glow_decoder_state_dict(
     in_channels: int = GLOW_TTS_DECODER["in_channels"],
     hidden_channels: int = GLOW_TTS_DECODER["hidden_channels"],
