@@ -750,6 +750,93 @@ int tts_op_melgan_block_tile(void);
 int tts_pqmf_synthesis(const float* d_x, int B, int bands, int L, const float* d_G, int taps, float* d_out,
                        void* hip_stream);
 
+/* ---- Multi-head self-attention of nn.MultiheadAttention (the FFTransformer layers of ForwardTTS /
+ * FastPitch; TTS/tts/layers/generic/transformer.py), online softmax on the matrix cores ----
+ *   d_out[b][h dk + d][i] = sum_j softmax_j((q_i dk^-0.5) . k_j) v_j[d],  dk = E / heads
+ * d_qkv [B][3E][T] fp32, rows q | k | v (the in_proj output), head h at channels h dk ...; the dk^-0.5
+ * query scale is applied by the op.  d_key_lengths: NULL (every key j < T counts) or [B] int64 on the
+ * device, values in [1, T]: keys j >= d_key_lengths[b] get probability exactly 0 (the key padding
+ * mask); every query i < T is computed, padded ones included.  d_out [B][E][T] fp32, not aliased.
+ * Head sizes dk: 32, 64, 128, 192, 256 or 384, with E <= 512 (TTS_ERR_UNSUPPORTED otherwise); any T
+ * with 3 E T 4 bytes below 2 GiB.  math_mode TTS_MATH_FP32_X6 or TTS_MATH_BF16 (TTS_MATH_FP32 and
+ * TTS_MATH_FP32_F16X3 run the fp32x6 kernel: both are held to the fp32 parity gates).  Results do
+ * not depend on B.  Stream-ordered; does not synchronise. */
+int tts_op_mha(const float* d_qkv, const int64_t* d_key_lengths, int B, int E, int heads, int T, int math_mode,
+               float* d_out, void* hip_stream);
+/* Queries one workgroup of the attention kernel computes. */
+int tts_op_mha_tile(void);
+
+/* ---- ForwardTTS (FastPitch / FastSpeech; TTS/tts/models/forward_tts.py, inference) with the
+ * "fftransformer" encoder and decoder ----
+ * Mirrors ForwardTTSArgs; encoder_* / decoder_* are encoder_params / decoder_params
+ * (hidden_channels_ffn, num_heads, num_layers).  The FFN convs have kernel size 3 (FFTransformer's
+ * kernel_size_fft default; FFTransformerBlock passes no other).  The text side (encoder, duration
+ * and pitch predictors) always runs TTS_MATH_FP32_X6, so the durations do not depend on math_mode;
+ * math_mode selects the decoder's arithmetic: TTS_MATH_BF16, or fp32x6 for every other mode.
+ * Head sizes hidden_channels / num_heads as tts_op_mha; hidden_channels <= 512. */
+#define TTS_FORWARD_TTS_MAX_FRAMES 5000 /* PositionalEncoding max_len: the pe buffer is [1][H][5000] */
+typedef struct TtsForwardTtsCfg {
+  int num_chars;
+  int out_channels;    /* 80 */
+  int hidden_channels; /* 384 */
+  int encoder_ffn_channels, encoder_num_heads, encoder_num_layers; /* 1024, 1, 6 */
+  int decoder_ffn_channels, decoder_num_heads, decoder_num_layers; /* 1024, 1, 6 */
+  int duration_predictor_hidden_channels, duration_predictor_kernel_size; /* 256, 3 */
+  int use_pitch;                                                      /* 1 (FastPitch); 0: FastSpeech */
+  int pitch_predictor_hidden_channels, pitch_predictor_kernel_size;   /* 256, 3 */
+  int pitch_embedding_kernel_size;                                    /* 3 */
+  int positional_encoding; /* 1: the decoder input is x sqrt(H) + pe * y_mask */
+  int num_speakers;        /* rows of emb_g.weight (use_speaker_embedding); 0: no speaker embedding */
+  int math_mode;
+} TtsForwardTtsCfg;
+
+/* Host weight order, H = hidden_channels, per FFTransformer layer (F = its ffn channels):
+ *   self_attn.in_proj_weight [3H][H], in_proj_bias [3H], self_attn.out_proj.weight [H][H], .bias [H],
+ *   conv1.weight [F][H][3], conv1.bias [F], conv2.weight [H][F][3], conv2.bias [H],
+ *   norm1.weight [H], norm1.bias [H], norm2.weight [H], norm2.bias [H]
+ * emb.weight [num_chars][H]; the encoder's layers; pos_encoder.pe [H][5000] (positional_encoding);
+ * the decoder's layers; postnet.weight [out][H][1], postnet.bias [out]; duration_predictor (the
+ * 10 tensors of TtsVitsDpCfg's order, no cond layers); with use_pitch: pitch_predictor (the same),
+ * pitch_emb.weight [H][1][k], pitch_emb.bias [H]; emb_g.weight [num_speakers][H] (num_speakers > 0). */
+int tts_forward_tts_num_weights(const TtsForwardTtsCfg* cfg);
+int64_t tts_forward_tts_weight_numel(const TtsForwardTtsCfg* cfg, int index);
+int tts_forward_tts_create(const TtsForwardTtsCfg* cfg, const float* const* host_weights, int device, void** handle);
+int tts_forward_tts_destroy(void* handle);
+/* Everything before the host read of y_lengths.  d_tokens [B][T_en] int64, d_x_lengths [B] int64 (the
+ * reference takes every token as valid: pass T_en; shorter lengths mask the encoder's keys and give
+ * the padded tokens no frames), d_speaker_ids [B] int64 (NULL when num_speakers == 0),
+ * d_given_durations [B][T_en] fp32 or NULL (used in place of the predicted ones).  Outputs:
+ * d_o_en [B][H][T_en] (encoder(emb) * x_mask + emb_g, + pitch_emb(pitch) with use_pitch), d_x_mask
+ * [B][T_en], d_durations_log [B][T_en], d_pitch [B][T_en] (NULL without use_pitch), d_durations
+ * [B][T_en] = round(max((exp(log) - 1) * x_mask * length_scale, 1)) (half to even) * x_mask,
+ * d_y_lengths [B] int64 = their sums. */
+int tts_forward_tts_encode(void* handle, const int64_t* d_tokens, const int64_t* d_x_lengths,
+                           const int64_t* d_speaker_ids, const float* d_given_durations, int B, int T_en,
+                           float length_scale, float* d_o_en, float* d_x_mask, float* d_durations_log, float* d_pitch,
+                           float* d_durations, int64_t* d_y_lengths, void* hip_stream);
+int tts_forward_tts_encode_profiled(void* handle, const int64_t* d_tokens, const int64_t* d_x_lengths,
+                                    const int64_t* d_speaker_ids, const float* d_given_durations, int B, int T_en,
+                                    float length_scale, float* d_o_en, float* d_x_mask, float* d_durations_log,
+                                    float* d_pitch, float* d_durations, int64_t* d_y_lengths, void* hip_stream,
+                                    TtsLaunchRecord* records, int max_records, int* n_records);
+/* The frames: expansion of d_o_en by d_durations, positional encoding, decoder, postnet.  T_de >=
+ * max(y_lengths), at most TTS_FORWARD_TTS_MAX_FRAMES with the positional encoding (TTS_ERR_INVALID
+ * beyond, the reference's RuntimeError).  mask_decoder_keys = 0 is the reference (its decoder block
+ * is called without a mask: queries attend over the padded frames too); 1 masks the keys past
+ * y_lengths.  d_out [B][out_channels][T_de], d_attn [B][T_en][T_de] (or NULL), d_y_mask [B][T_de]. */
+int tts_forward_tts_decode(void* handle, const float* d_o_en, const float* d_durations, const float* d_x_mask,
+                           const int64_t* d_y_lengths, int B, int T_en, int T_de, int mask_decoder_keys, float* d_out,
+                           float* d_attn, float* d_y_mask, void* hip_stream);
+int tts_forward_tts_decode_profiled(void* handle, const float* d_o_en, const float* d_durations, const float* d_x_mask,
+                                    const int64_t* d_y_lengths, int B, int T_en, int T_de, int mask_decoder_keys,
+                                    float* d_out, float* d_attn, float* d_y_mask, void* hip_stream,
+                                    TtsLaunchRecord* records, int max_records, int* n_records);
+/* d_y [B][H][T] = FFTransformerBlock(d_x [B][H][T]) of the encoder (decoder = 0, fp32x6) or the decoder
+ * (decoder = 1, its math mode); d_key_lengths [B] int64 or NULL (no key padding mask).  Every column
+ * is computed, the padded ones included. */
+int tts_forward_tts_block(void* handle, int decoder, const float* d_x, const int64_t* d_key_lengths, int B, int T,
+                          float* d_y, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,8 @@
 #include <string>
 #include <vector>
 
+#include "fft_attn.hpp"
+#include "forward_tts.hpp"
 #include "glow.hpp"
 #include "handoff.hpp"
 #include "hifigan.hpp"
@@ -1067,6 +1069,123 @@ int tts_pqmf_synthesis(const float* d_x, int B, int bands, int L, const float* d
                        void* hip_stream) {
   return guarded([&] {
     tts::launch_pqmf_synthesis(d_x, B, bands, L, d_G, taps, d_out, static_cast<hipStream_t>(hip_stream));
+  });
+}
+
+int tts_op_mha(const float* d_qkv, const int64_t* d_key_lengths, int B, int E, int heads, int T, int math_mode,
+               float* d_out, void* hip_stream) {
+  return guarded([&] {
+    TTS_REQUIRE(d_qkv && d_out, 1, "NULL argument");
+    TTS_REQUIRE(math_mode >= tts::MATH_FP32 && math_mode <= tts::MATH_LAST, 1, "unknown math_mode");
+    const int mode = math_mode == tts::MATH_BF16 ? tts::MATH_BF16 : tts::MATH_FP32_X6;
+    tts::launch_mha(mode, d_qkv, d_key_lengths, d_out, B, E, heads, T, static_cast<hipStream_t>(hip_stream));
+  });
+}
+
+int tts_op_mha_tile(void) { return tts::kMhaTile; }
+
+int tts_forward_tts_num_weights(const TtsForwardTtsCfg* cfg) {
+  int n = -1;
+  int st = guarded([&] {
+    TTS_REQUIRE(cfg, 1, "NULL cfg");
+    tts::forward_tts_validate(*cfg);
+    n = (int)tts::forward_tts_weight_shapes(*cfg).size();
+  });
+  return st == TTS_OK ? n : -st;
+}
+
+int64_t tts_forward_tts_weight_numel(const TtsForwardTtsCfg* cfg, int idx) {
+  int64_t n = -1;
+  guarded([&] {
+    TTS_REQUIRE(cfg, 1, "NULL cfg");
+    tts::forward_tts_validate(*cfg);
+    auto s = tts::forward_tts_weight_shapes(*cfg);
+    TTS_REQUIRE(idx >= 0 && idx < (int)s.size(), 1, "weight index out of range");
+    n = s[idx];
+  });
+  return n;
+}
+
+int tts_forward_tts_create(const TtsForwardTtsCfg* cfg, const float* const* host_weights, int device, void** handle) {
+  return guarded([&] {
+    TTS_REQUIRE(cfg && host_weights && handle, 1, "NULL argument");
+    *handle = nullptr;
+    *handle = new tts::ForwardTts(*cfg, host_weights, device);
+  });
+}
+
+int tts_forward_tts_destroy(void* handle) {
+  return guarded([&] { delete static_cast<tts::ForwardTts*>(handle); });
+}
+
+int tts_forward_tts_encode(void* handle, const int64_t* d_tokens, const int64_t* d_x_lengths,
+                           const int64_t* d_speaker_ids, const float* d_given_durations, int B, int T_en,
+                           float length_scale, float* d_o_en, float* d_x_mask, float* d_durations_log, float* d_pitch,
+                           float* d_durations, int64_t* d_y_lengths, void* hip_stream) {
+  return guarded([&] {
+    TTS_REQUIRE(handle, 1, "NULL handle");
+    static_cast<tts::ForwardTts*>(handle)->encode(d_tokens, d_x_lengths, d_speaker_ids, d_given_durations, B, T_en,
+                                                  length_scale, d_o_en, d_x_mask, d_durations_log, d_pitch,
+                                                  d_durations, d_y_lengths, static_cast<hipStream_t>(hip_stream));
+  });
+}
+
+int tts_forward_tts_encode_profiled(void* handle, const int64_t* d_tokens, const int64_t* d_x_lengths,
+                                    const int64_t* d_speaker_ids, const float* d_given_durations, int B, int T_en,
+                                    float length_scale, float* d_o_en, float* d_x_mask, float* d_durations_log,
+                                    float* d_pitch, float* d_durations, int64_t* d_y_lengths, void* hip_stream,
+                                    TtsLaunchRecord* records, int max_records, int* n_records) {
+  return guarded([&] {
+    TTS_REQUIRE(handle && n_records, 1, "NULL argument");
+    auto* h = static_cast<tts::ForwardTts*>(handle);
+    auto s = static_cast<hipStream_t>(hip_stream);
+    tts::Profiler prof;
+    {
+      tts::DeviceGuard g(h->device());
+      h->encode(d_tokens, d_x_lengths, d_speaker_ids, d_given_durations, B, T_en, length_scale, d_o_en, d_x_mask,
+                d_durations_log, d_pitch, d_durations, d_y_lengths, s, &prof);
+      TTS_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    export_records(prof, records, max_records, n_records);
+  });
+}
+
+int tts_forward_tts_decode(void* handle, const float* d_o_en, const float* d_durations, const float* d_x_mask,
+                           const int64_t* d_y_lengths, int B, int T_en, int T_de, int mask_decoder_keys, float* d_out,
+                           float* d_attn, float* d_y_mask, void* hip_stream) {
+  return guarded([&] {
+    TTS_REQUIRE(handle, 1, "NULL handle");
+    static_cast<tts::ForwardTts*>(handle)->decode(d_o_en, d_durations, d_x_mask, d_y_lengths, B, T_en, T_de,
+                                                  mask_decoder_keys != 0, d_out, d_attn, d_y_mask,
+                                                  static_cast<hipStream_t>(hip_stream));
+  });
+}
+
+int tts_forward_tts_decode_profiled(void* handle, const float* d_o_en, const float* d_durations, const float* d_x_mask,
+                                    const int64_t* d_y_lengths, int B, int T_en, int T_de, int mask_decoder_keys,
+                                    float* d_out, float* d_attn, float* d_y_mask, void* hip_stream,
+                                    TtsLaunchRecord* records, int max_records, int* n_records) {
+  return guarded([&] {
+    TTS_REQUIRE(handle && n_records, 1, "NULL argument");
+    auto* h = static_cast<tts::ForwardTts*>(handle);
+    auto s = static_cast<hipStream_t>(hip_stream);
+    tts::Profiler prof;
+    {
+      tts::DeviceGuard g(h->device());
+      h->decode(d_o_en, d_durations, d_x_mask, d_y_lengths, B, T_en, T_de, mask_decoder_keys != 0, d_out, d_attn,
+                d_y_mask, s, &prof);
+      TTS_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    export_records(prof, records, max_records, n_records);
+  });
+}
+
+int tts_forward_tts_block(void* handle, int decoder, const float* d_x, const int64_t* d_key_lengths, int B, int T,
+                          float* d_y, void* hip_stream) {
+  return guarded([&] {
+    TTS_REQUIRE(handle, 1, "NULL handle");
+    static_cast<tts::ForwardTts*>(handle)->block(decoder != 0, d_x, d_key_lengths, B, T, d_y,
+                                                 static_cast<hipStream_t>(hip_stream));
   });
 }
 

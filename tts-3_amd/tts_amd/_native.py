@@ -216,6 +216,32 @@ class TtsVitsDpCfg(Structure):
     ]
 
 
+FORWARD_TTS_MAX_FRAMES = 5000
+
+
+class TtsForwardTtsCfg(Structure):
+    _fields_ = [
+        ("num_chars", c_int),
+        ("out_channels", c_int),
+        ("hidden_channels", c_int),
+        ("encoder_ffn_channels", c_int),
+        ("encoder_num_heads", c_int),
+        ("encoder_num_layers", c_int),
+        ("decoder_ffn_channels", c_int),
+        ("decoder_num_heads", c_int),
+        ("decoder_num_layers", c_int),
+        ("duration_predictor_hidden_channels", c_int),
+        ("duration_predictor_kernel_size", c_int),
+        ("use_pitch", c_int),
+        ("pitch_predictor_hidden_channels", c_int),
+        ("pitch_predictor_kernel_size", c_int),
+        ("pitch_embedding_kernel_size", c_int),
+        ("positional_encoding", c_int),
+        ("num_speakers", c_int),
+        ("math_mode", c_int),
+    ]
+
+
 class TtsLaunchRecord(Structure):
     _fields_ = [("name", c_char * 48), ("flops", c_double), ("bytes", c_double), ("ms", c_float)]
 
@@ -430,6 +456,33 @@ SIGNATURES = {
     ),
     "tts_op_melgan_block_tile": (c_int, []),
     "tts_pqmf_synthesis": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "tts_op_mha": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "tts_op_mha_tile": (c_int, []),
+    "tts_forward_tts_num_weights": (c_int, [POINTER(TtsForwardTtsCfg)]),
+    "tts_forward_tts_weight_numel": (c_int64, [POINTER(TtsForwardTtsCfg), c_int]),
+    "tts_forward_tts_create": (c_int, [POINTER(TtsForwardTtsCfg), POINTER(c_void_p), c_int, POINTER(c_void_p)]),
+    "tts_forward_tts_destroy": (c_int, [c_void_p]),
+    "tts_forward_tts_encode": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    "tts_forward_tts_encode_profiled": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_void_p, POINTER(TtsLaunchRecord), c_int, POINTER(c_int)],
+    ),
+    "tts_forward_tts_decode": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+         c_void_p],
+    ),
+    "tts_forward_tts_decode_profiled": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+         c_void_p, POINTER(TtsLaunchRecord), c_int, POINTER(c_int)],
+    ),
+    "tts_forward_tts_block": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -9,6 +9,7 @@ JSON reader (no coqpit dependency).
   (TTS/tts/models/vits.py:545-565, built at :675-682 and :704-718)
 * ``VITS_TEXT_ENCODER`` / ``VITS_SDP`` / ``VITS_INFERENCE``: the text side of ``Vits.inference``
   (vits.py:653-692, :1088-1174)
+* ``FAST_PITCH``: ``ForwardTTSArgs`` (TTS/tts/models/forward_tts.py), the FastPitch defaults
 """
 from __future__ import annotations
 
@@ -110,6 +111,32 @@ VITS_DECODER: Dict[str, Any] = {
     "conv_pre_weight_norm": False,
     "conv_post_weight_norm": False,
     "conv_post_bias": False,
+}
+
+# ForwardTTSArgs defaults (TTS/tts/models/forward_tts.py): FastPitch
+FAST_PITCH: Dict[str, Any] = {
+    "num_chars": None,
+    "out_channels": 80,
+    "hidden_channels": 384,
+    "use_aligner": True,
+    "use_pitch": True,
+    "pitch_predictor_hidden_channels": 256,
+    "pitch_predictor_kernel_size": 3,
+    "pitch_predictor_dropout_p": 0.1,
+    "pitch_embedding_kernel_size": 3,
+    "use_energy": False,
+    "duration_predictor_hidden_channels": 256,
+    "duration_predictor_kernel_size": 3,
+    "duration_predictor_dropout_p": 0.1,
+    "positional_encoding": True,
+    "length_scale": 1,
+    "encoder_type": "fftransformer",
+    "encoder_params": {"hidden_channels_ffn": 1024, "num_heads": 1, "num_layers": 6, "dropout_p": 0.1},
+    "decoder_type": "fftransformer",
+    "decoder_params": {"hidden_channels_ffn": 1024, "num_heads": 1, "num_layers": 6, "dropout_p": 0.1},
+    "num_speakers": 1,
+    "use_speaker_embedding": False,
+    "use_d_vector_file": False,
 }
 
 

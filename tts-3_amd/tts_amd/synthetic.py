@@ -618,6 +618,73 @@ def vits_dp_state_dict(
     return sd
 
 
+def forward_tts_state_dict(args, seed: int = 2024, attn_scale: float = 1.6) -> "OrderedDict[str, torch.Tensor]":
+    """State dict of ``ForwardTTS`` (``args``: a ``ForwardTTSArgs`` or a dict with its fields) with the
+    reference's keys: variance-preserving convs (conv2 of an FFN makes up for the ReLU), the q and k
+    rows of every in_proj scaled so a layer's scores have standard deviation about ``attn_scale ** 2``
+    (a peaked softmax; the first decoder layer reads x sqrt(H) + pe, so its rows are scaled down by
+    that input's rms), a light out_proj (the attention branch enters twice and averages columns),
+    LayerNorm gains ~ 1 + 0.1 N and biases ~ 0.1 N, a duration predictor whose
+    proj spreads exp(o) - 1 over about 1 ... 8 frames, a pitch predictor with output of O(1)."""
+    a = args if isinstance(args, dict) else vars(args)
+    H, out = a["hidden_channels"], a["out_channels"]
+    rng = np.random.default_rng(seed)
+    sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+
+    def t(v):
+        return torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32))
+
+    def conv(name, cout, cin, k, scale=1.0, bias_std=0.02):
+        sd[f"{name}.weight"] = t(rng.standard_normal((cout, cin, k)) * (scale / np.sqrt(cin * k)))
+        sd[f"{name}.bias"] = t(rng.standard_normal((cout,)) * bias_std)
+
+    def block(pre, params, first_input_rms):
+        F = params["hidden_channels_ffn"]
+        for i in range(params["num_layers"]):
+            p = f"{pre}fft_layers.{i}."
+            rms = first_input_rms if i == 0 else 1.0
+            w = rng.standard_normal((3 * H, H)) / (np.sqrt(H) * rms)
+            w[: 2 * H] *= attn_scale
+            sd[p + "self_attn.in_proj_weight"] = t(w)
+            sd[p + "self_attn.in_proj_bias"] = t(rng.standard_normal(3 * H) * 0.02)
+            # the attention branch enters twice (LN(x + 2 a)) and averages columns: at full weight the
+            # columns of a deep stack converge and its softmax flattens
+            sd[p + "self_attn.out_proj.weight"] = t(rng.standard_normal((H, H)) * (0.12 / np.sqrt(H)))
+            sd[p + "self_attn.out_proj.bias"] = t(rng.standard_normal(H) * 0.02)
+            conv(p + "conv1", F, H, 3)
+            conv(p + "conv2", H, F, 3, scale=np.sqrt(2.0))
+            for n in ("norm1", "norm2"):
+                sd[p + n + ".weight"] = t(1.0 + 0.1 * rng.standard_normal(H))
+                sd[p + n + ".bias"] = t(0.1 * rng.standard_normal(H))
+
+    def predictor(pre, hidden, k, proj_scale, proj_bias):
+        d = vits_dp_state_dict(H, hidden, k, seed=int(rng.integers(1 << 30)), log_duration=proj_bias)
+        d["proj.weight"] = d["proj.weight"] * (proj_scale / 0.3)
+        for key, v in d.items():
+            sd[pre + key] = v
+
+    sd["emb.weight"] = t(rng.standard_normal((a["num_chars"], H)))
+    block("encoder.encoder.", a["encoder_params"], 1.0)
+    if a.get("positional_encoding", True):
+        pe = torch.zeros(5000, H)
+        position = torch.arange(0, 5000).unsqueeze(1)
+        div_term = torch.pow(10000, torch.arange(0, H, 2).float() / H)
+        pe[:, 0::2] = torch.sin(position.float() / div_term)
+        pe[:, 1::2] = torch.cos(position.float() / div_term)
+        sd["pos_encoder.pe"] = pe.unsqueeze(0).transpose(1, 2).contiguous()
+    block("decoder.decoder.transformer_block.", a["decoder_params"],
+          float(np.sqrt(H + 0.5)) if a.get("positional_encoding", True) else 1.0)
+    conv("decoder.decoder.postnet", out, H, 1)
+    predictor("duration_predictor.", a["duration_predictor_hidden_channels"], a["duration_predictor_kernel_size"],
+              0.5, 1.3)
+    if a.get("use_pitch", True):
+        predictor("pitch_predictor.", a["pitch_predictor_hidden_channels"], a["pitch_predictor_kernel_size"], 1.0, 0.0)
+        conv("pitch_emb", H, 1, a["pitch_embedding_kernel_size"], scale=0.5)
+    if a.get("use_speaker_embedding", False):
+        sd["emb_g.weight"] = t(rng.standard_normal((a["num_speakers"], H)) * 0.3)
+    return sd
+
+
 def tokens(batch: int, length: int, num_chars: int, seed: int = 0) -> torch.Tensor:
     """Synthetic token ids [B, T] uniform in [0, num_chars) (int64, CPU)."""
     g = torch.Generator().manual_seed(seed)

@@ -3,7 +3,10 @@
 with ``maximum_path`` (Monotonic Alignment Search), and the VITS ``ResidualCouplingBlocks`` flow
 (both directions), ``PosteriorEncoder``, the linear spectrogram ``wav_to_spec`` and ``Vits``
 (``inference``, ``voice_conversion``, ``inference_voice_conversion``) with its text side
-(``TextEncoder``, ``StochasticDurationPredictor``), on MI355X."""
+(``TextEncoder``, ``StochasticDurationPredictor``), and ``ForwardTTS`` (FastPitch / FastSpeech:
+``inference``) with the self-attention of its ``FFTransformer`` layers, ``multi_head_attention``, on
+MI355X."""
+from .forward_tts import ForwardTTS, ForwardTTSArgs, multi_head_attention
 from .glow_decoder import Decoder
 from .glow_tts import Encoder, GlowTTS
 from .helpers import maximum_path
@@ -12,5 +15,6 @@ from .vits_flow import PosteriorEncoder, ResidualCouplingBlocks
 from .vits_text import DurationPredictor, StochasticDurationPredictor, TextEncoder, Vits
 from .xtts_decoder import HifiDecoder
 
-__all__ = ["Decoder", "DurationPredictor", "Encoder", "GlowTTS", "HifiDecoder", "PosteriorEncoder", "ResidualCouplingBlocks",
-           "StochasticDurationPredictor", "TextEncoder", "Vits", "maximum_path", "wav_to_spec", "wav_to_spec_profile"]
+__all__ = ["Decoder", "DurationPredictor", "Encoder", "ForwardTTS", "ForwardTTSArgs", "GlowTTS", "HifiDecoder", "PosteriorEncoder", "ResidualCouplingBlocks",
+           "StochasticDurationPredictor", "TextEncoder", "Vits", "maximum_path", "multi_head_attention", "wav_to_spec",
+           "wav_to_spec_profile"]
