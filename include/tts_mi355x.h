@@ -756,7 +756,9 @@ int tts_pqmf_synthesis(const float* d_x, int B, int bands, int L, const float* d
  * d_qkv [B][3E][T] fp32, rows q | k | v (the in_proj output), head h at channels h dk ...; the dk^-0.5
  * query scale is applied by the op.  d_key_lengths: NULL (every key j < T counts) or [B] int64 on the
  * device, values in [1, T]: keys j >= d_key_lengths[b] get probability exactly 0 (the key padding
- * mask); every query i < T is computed, padded ones included.  d_out [B][E][T] fp32, not aliased.
+ * mask); every query i < T is computed, padded ones included.  A length outside [1, T] is clamped to
+ * [0, T]; an item of length 0 has no key to attend to and its d_out is all zeros (an invalid item
+ * gives zeros, not the NaN of a softmax over nothing).  d_out [B][E][T] fp32, not aliased.
  * Head sizes dk: 32, 64, 128, 192, 256 or 384, with E <= 512 (TTS_ERR_UNSUPPORTED otherwise); any T
  * with 3 E T 4 bytes below 2 GiB.  math_mode TTS_MATH_FP32_X6 or TTS_MATH_BF16 (TTS_MATH_FP32 and
  * TTS_MATH_FP32_F16X3 run the fp32x6 kernel: both are held to the fp32 parity gates).  Results do

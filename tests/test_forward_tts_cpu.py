@@ -307,3 +307,96 @@ def test_condition_c_oracle_fp32_within_half_the_gates(name):
             print(f"{name} {variant} {key}: oracle fp32 vs fp64 max|d|={ma:.3e} rel-RMS={rr:.3e}")
             assert ma <= WAV_MAX_ABS / 2 and rr <= FP32_REL_RMS / 2, (variant, key)
         assert torch.equal(f32["alignments"].double(), ref["alignments"])
+
+
+# ------------------------------------------------------------------ conditions on the long GPU tests' inputs
+def long_predicted_variants(name):
+    """The variants whose durations differ (the decoder's key mask does not reach the durations)."""
+    return [v for v in C.LONG_VARIANTS[name] if "+" not in v]
+
+
+@pytest.mark.parametrize("name", ["small_long", "wide_long"])
+def test_condition_b_long_durations_are_away_from_the_rounding_edges(name):
+    """Condition (b) for the long cases (test_forward_tts_long_gpu.py), without and - small_long - with
+    every token valid: before rounding the oracle's durations are at least 1e-3 from any half-integer and
+    from the clamp at 1, its fp32 and fp64 durations are equal, and the frame counts are the documented
+    ones (several 256-frame workgroups, more than one conv tile)."""
+    for variant in long_predicted_variants(name):
+        ref, f32 = C.long_reference(name, variant), C.long_reference(name, variant, fp32=True)
+        raw = ref["durations_raw"]
+        valid = raw != 0
+        above = raw[valid & (raw > 1)]
+        half = ((above - torch.floor(above)) - 0.5).abs().min().item()
+        clamp = (raw[valid] - 1.0).abs().min().item()
+        frames = tuple(int(v) for v in ref["durations"].sum(1))
+        print(f"{name} {variant}: frames {frames}, distance from a half-integer {half:.2e}, from the clamp {clamp:.2e}")
+        assert half >= 1e-3 and clamp >= 1e-3, variant
+        assert torch.equal(ref["durations"], f32["durations"].double())
+        assert frames == C.LONG_FRAMES[name, variant]
+        assert ref["durations"].max() >= 4 and ref["durations"][ref["durations"] > 0].min() <= 2
+        if variant == "lengths":  # padded tokens get no frames
+            pad = torch.arange(raw.shape[1])[None, :] >= torch.tensor(C.LONG[name]["lengths"])[:, None]
+            assert pad.any() and (ref["durations"][pad] == 0).all()
+
+
+@pytest.mark.parametrize("name", ["small_long", "wide_long"])
+def test_condition_c_long_oracle_fp32_within_half_the_gates(name):
+    """Condition (c) for the long cases: the oracle's own fp32 forward is within half of each fp32 gate."""
+    for variant in C.LONG_VARIANTS[name]:
+        ref, f32 = C.long_reference(name, variant), C.long_reference(name, variant, fp32=True)
+        for key in ("model_outputs", "pitch", "durations_log"):
+            ma, rr = max_abs(f32[key], ref[key]), rel_rms(f32[key], ref[key])
+            print(f"{name} {variant} {key}: oracle fp32 vs fp64 max|d|={ma:.3e} rel-RMS={rr:.3e}")
+            assert ma <= WAV_MAX_ABS / 2 and rr <= FP32_REL_RMS / 2, (variant, key)
+        assert torch.equal(f32["alignments"].double(), ref["alignments"])
+
+
+@pytest.mark.parametrize("name", ["small", "wide"])
+def test_condition_c_long_block_inputs(name):
+    """The same for the block tests' inputs at T = 259, ragged ([259, 129] keys) and unmasked."""
+    for decoder in (False, True):
+        for ragged in (True, False):
+            ref = C.long_block_reference(name, decoder, ragged)
+            f32 = C.long_block_reference(name, decoder, ragged, fp32=True)
+            assert ref.shape == (2, C.ARGS[name]["hidden_channels"], C.LONG_BLOCK_T)
+            ma, rr = max_abs(f32, ref), rel_rms(f32, ref)
+            print(f"{name} {'decoder' if decoder else 'encoder'} block T={C.LONG_BLOCK_T} "
+                  f"{'ragged' if ragged else 'no mask'}: oracle fp32 vs fp64 max|d|={ma:.3e} rel-RMS={rr:.3e}")
+            assert ma <= WAV_MAX_ABS / 2 and rr <= FP32_REL_RMS / 2
+    assert C.block_case(name, True, C.LONG_BLOCK_T)[3].tolist() == [259, 129]
+
+
+@pytest.mark.parametrize("keys", [False, True])
+def test_condition_c_frame_limit_case(keys):
+    """The 5000-frame case: the durations sum to the positional encoding's length exactly, and the
+    oracle's fp32 forward is within half of the fp32 gates there too."""
+    assert sum(C.LIMIT_DURATIONS) == R.MAX_FRAMES and len(C.LIMIT_DURATIONS) == 13
+    ref, f32 = C.limit_reference(keys), C.limit_reference(keys, fp32=True)
+    assert ref["model_outputs"].shape == (1, R.MAX_FRAMES, 80)
+    ma, rr = max_abs(f32["model_outputs"], ref["model_outputs"]), rel_rms(f32["model_outputs"], ref["model_outputs"])
+    print(f"frame limit, keys masked {keys}: oracle fp32 vs fp64 max|d|={ma:.3e} rel-RMS={rr:.3e}")
+    assert ma <= WAV_MAX_ABS / 2 and rr <= FP32_REL_RMS / 2
+    assert torch.equal(f32["alignments"].double(), ref["alignments"])
+
+
+def test_bf16_analogue_decides_the_long_bf16_gate():
+    """Condition (c) for bf16 on small_long lengths+keys, by the rule of
+    test_bf16_analogue_decides_the_bf16_gates: gated where torch's own bf16 CPU forward of the decoder
+    (keys masked, as the case runs) stays inside half of the bf16 gates, logged only where it does not."""
+    from _util import BF16_MAX_ABS, BF16_REL_RMS
+
+    ref = C.long_reference("small_long", "lengths+keys")
+    with torch.no_grad():
+        out = R.decoder(C.state_dict("small"), C.ARGS["small"], ref["decoder_input"], ref["y_mask"],
+                        mask_decoder_keys=True, dtype=torch.bfloat16)
+    ma, rr = max_abs(out.double(), ref["model_outputs"]), rel_rms(out.double(), ref["model_outputs"])
+    inside = ma <= BF16_MAX_ABS / 2 and rr <= BF16_REL_RMS / 2
+    print(f"small_long lengths+keys: torch bf16 decoder vs fp64 max|d|={ma:.3e} rel-RMS={rr:.3e} inside half the gate: {inside}")
+    assert inside == C.LONG_BF16_GATED["small_long"]
+
+
+def test_long_mha_shapes_rejected_before_any_launch():
+    """Valid head sizes (192, 384) with more than 512 channels; 512 channels are accepted shapes."""
+    assert call(576, 3, 8) == N.TTS_ERR_UNSUPPORTED
+    assert call(768, 2, 8) == N.TTS_ERR_UNSUPPORTED
+    assert b"512" in N.lib().tts_last_error()

@@ -18,8 +18,9 @@ bool mha_head_size_ok(int dk);
 // (key_len == nullptr: every j < T), for every query i < T, padded ones included.
 //   qkv: [B][3E][T] fp32, rows q | k | v, head h at channels h dk .. h dk + dk - 1 (the layout
 //        launch_attention takes); the dk^-0.5 query scale is applied here, not by the caller
-//   key_len: [B] int64 on the device, values in [1, T] (larger values count as T; with 0 keys the
-//        row is NaN, as the reference's softmax over an all -inf row is)
+//   key_len: [B] int64 on the device, values in [1, T] (larger values count as T, negative ones as 0;
+//        with 0 keys the item's output is all zeros: an invalid item gives zeros, where the
+//        reference's softmax over an all -inf row is NaN)
 //   out: [B][E][T] fp32, must not alias qkv
 // mode: MATH_FP32_X6 or MATH_BF16.  Results do not depend on B.
 void launch_mha(int mode, const float* qkv, const int64_t* key_len, float* out, int B, int E, int heads, int T,

@@ -26,6 +26,7 @@
 // second product (at one wave per SIMD nothing else hides their latency).
 // The scores never leave the workgroup, no buffer holds a whole score row (no limit on T), and
 // every sum runs in one fixed order, so a batch item's result does not depend on the batch.
+// key_len is clamped to [0, T]; an item with no key (length 0) writes zeros.
 //
 // Math: SchemeX6 (three exact bf16 pieces per fp32 operand - Q, K, P and V -, the six products with
 // i + j <= 2 into one accumulator, smallest first) or SchemeB1 (single bf16 products).
@@ -257,7 +258,8 @@ __global__ __launch_bounds__(256) void mha_kernel(MhaArgs a) {
 
   // ---- out = O / l ----
   const rsrc_t ry = make_rsrc(a.out + (size_t)b * E * T, (unsigned)E * uT * 4u);
-  const float inv = 1.f / l_run;
+  // no key at all (key_len 0: the loop above never ran, O = 0 and l = 0): zeros, not 0 / 0
+  const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
 #pragma unroll
   for (int i = 0; i < NOB; ++i) {
     const int ob = 2 * i + dh;

@@ -53,7 +53,9 @@ def multi_head_attention(qkv: torch.Tensor, num_heads: int, key_lengths: torch.T
     [B, E, T], the heads' outputs before ``out_proj``.  The ``dk ** -0.5`` query scale is applied here.
 
     ``key_lengths`` [B] (integer, values in [1, T]) is the key padding mask ``~sequence_mask(key_lengths)``:
-    keys past an utterance's length get probability exactly 0; every query column is computed.
+    keys past an utterance's length get probability exactly 0; every query column is computed.  A length
+    outside [1, T] is clamped to [0, T]; an item of length 0 (no key at all) comes out all zeros, where
+    torch's softmax over nothing gives NaN.
     ``math_mode``: ``"bf16"`` for single bf16 products; every other mode (the package default included)
     runs the fp32-faithful fp32x6 kernel."""
     _nat.require_device_tensor(qkv, "qkv")
