@@ -3,7 +3,6 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -58,18 +57,73 @@ void export_records(const tts::Profiler& prof, TtsLaunchRecord* records, int max
   }
 }
 
-// RAII device buffer for the single-op entry points.
-struct TmpDev {
-  float* p = nullptr;
-  explicit TmpDev(const float* host, size_t n) {
-    if (n == 0) return;
-    if (hipMalloc(&p, n * sizeof(float)) != hipSuccess) throw tts::Error(4, "hipMalloc failed");
-    if (host) TTS_HIP_CHECK(hipMemcpy(p, host, n * sizeof(float), hipMemcpyHostToDevice));
-  }
-  ~TmpDev() {
-    if (p) (void)hipFree(p);
-  }
-};
+// Device copy of n host floats on the current device (host == nullptr: left uninitialised), for
+// the single-op entry points.
+tts::DeviceBuffer to_device(const float* host, size_t n) {
+  tts::DeviceBuffer b;
+  int dev = 0;
+  TTS_HIP_CHECK(hipGetDevice(&dev));
+  b.grow(dev, n * sizeof(float), "operand");
+  if (host && n) TTS_HIP_CHECK(hipMemcpy(b.as<>(), host, n * sizeof(float), hipMemcpyHostToDevice));
+  return b;
+}
+
+// The entry points every handle family repeats.  validate and shapes take the cfg by reference.
+template <class Cfg, class Validate, class Shapes>
+int num_weights(const Cfg* cfg, Validate validate, Shapes shapes) {
+  int n = -1;
+  int st = guarded([&] {
+    TTS_REQUIRE(cfg, 1, "NULL cfg");
+    validate(*cfg);
+    n = (int)shapes(*cfg).size();
+  });
+  return st == TTS_OK ? n : -st;
+}
+
+template <class Cfg, class Validate, class Shapes>
+int64_t weight_numel(const Cfg* cfg, int idx, Validate validate, Shapes shapes) {
+  int64_t n = -1;
+  guarded([&] {
+    TTS_REQUIRE(cfg, 1, "NULL cfg");
+    validate(*cfg);
+    auto s = shapes(*cfg);
+    TTS_REQUIRE(idx >= 0 && idx < (int)s.size(), 1, "weight index out of range");
+    n = s[idx];
+  });
+  return n;
+}
+
+// host_weights: the weight pointer array, or the STFT's window
+template <class T, class Cfg, class W>
+int create(const Cfg* cfg, const W* host_weights, int device, void** handle) {
+  return guarded([&] {
+    TTS_REQUIRE(cfg && host_weights && handle, 1, "NULL argument");
+    *handle = nullptr;
+    *handle = new T(*cfg, host_weights, device);
+  });
+}
+
+template <class T>
+int destroy(void* handle) {
+  return guarded([&] { delete static_cast<T*>(handle); });
+}
+
+// A *_profiled entry point: body(T&, hipStream_t, Profiler*) is the executor call, timed per launch.
+template <class T, class Body>
+int profiled(void* handle, void* hip_stream, TtsLaunchRecord* records, int max_records, int* n_records, Body body) {
+  return guarded([&] {
+    TTS_REQUIRE(handle && n_records, 1, "NULL argument");
+    auto* h = static_cast<T*>(handle);
+    auto s = static_cast<hipStream_t>(hip_stream);
+    tts::Profiler prof;
+    {
+      tts::DeviceGuard g(h->device());
+      body(*h, s, &prof);
+      TTS_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    export_records(prof, records, max_records, n_records);
+  });
+}
 }  // namespace
 
 extern "C" {
@@ -80,39 +134,19 @@ const char* tts_build_target(void) { return "gfx950"; }
 
 // ----------------------------------------------------------------------------- HiFiGAN
 int tts_hifigan_num_weights(const TtsHifiganCfg* cfg) {
-  int n = -1;
-  int st = guarded([&] {
-    TTS_REQUIRE(cfg, 1, "NULL cfg");
-    tts::hifigan_validate(*cfg);
-    n = (int)tts::hifigan_weight_shapes(*cfg).size();
-  });
-  return st == TTS_OK ? n : -st;
+  return num_weights(cfg, tts::hifigan_validate, tts::hifigan_weight_shapes);
 }
 
 int64_t tts_hifigan_weight_numel(const TtsHifiganCfg* cfg, int idx) {
-  int64_t n = -1;
-  guarded([&] {
-    TTS_REQUIRE(cfg, 1, "NULL cfg");
-    tts::hifigan_validate(*cfg);
-    auto s = tts::hifigan_weight_shapes(*cfg);
-    TTS_REQUIRE(idx >= 0 && idx < (int)s.size(), 1, "weight index out of range");
-    n = s[idx];
-  });
-  return n;
+  return weight_numel(cfg, idx, tts::hifigan_validate, tts::hifigan_weight_shapes);
 }
 
 int tts_hifigan_create(const TtsHifiganCfg* cfg, const float* const* host_weights, int device,
                        void** handle) {
-  return guarded([&] {
-    TTS_REQUIRE(cfg && host_weights && handle, 1, "NULL argument");
-    *handle = nullptr;
-    *handle = new tts::Hifigan(*cfg, host_weights, device);
-  });
+  return create<tts::Hifigan>(cfg, host_weights, device, handle);
 }
 
-int tts_hifigan_destroy(void* handle) {
-  return guarded([&] { delete static_cast<tts::Hifigan*>(handle); });
-}
+int tts_hifigan_destroy(void* handle) { return destroy<tts::Hifigan>(handle); }
 
 int64_t tts_hifigan_output_length(const void* handle, int T, int pad) {
   if (!handle) return -1;
@@ -144,55 +178,32 @@ int tts_hifigan_forward(void* handle, const float* d_mel, int B, int C, int T, i
 int tts_hifigan_forward_profiled(void* handle, const float* d_mel, int B, int C, int T, int pad,
                                  const float* d_g, float* d_wav, void* hip_stream,
                                  TtsLaunchRecord* records, int max_records, int* n_records) {
-  return guarded([&] {
-    TTS_REQUIRE(handle && n_records, 1, "NULL argument");
-    auto* h = static_cast<tts::Hifigan*>(handle);
-    auto s = static_cast<hipStream_t>(hip_stream);
-    tts::Profiler prof;
-    {
-      tts::DeviceGuard g(h->device());
-      h->forward(d_mel, B, C, T, pad, d_g, d_wav, s, &prof);
-      TTS_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    export_records(prof, records, max_records, n_records);
-  });
+  auto body = [&](tts::Hifigan& h, hipStream_t s, tts::Profiler* prof) {
+    h.forward(d_mel, B, C, T, pad, d_g, d_wav, s, prof);
+  };
+  return profiled<tts::Hifigan>(handle, hip_stream, records, max_records, n_records, body);
 }
 
 // ----------------------------------------------------------------------------- Glow encoder + glue
+// with its defaults: the duration predictor included, the embedding as wide as the encoder
+static std::vector<int64_t> glow_encoder_shapes(const TtsGlowEncoderCfg& c) {
+  return tts::glow_encoder_weight_shapes(c);
+}
+
 int tts_glow_encoder_num_weights(const TtsGlowEncoderCfg* cfg) {
-  int n = -1;
-  int st = guarded([&] {
-    TTS_REQUIRE(cfg, 1, "NULL cfg");
-    tts::glow_encoder_validate(*cfg);
-    n = (int)tts::glow_encoder_weight_shapes(*cfg).size();
-  });
-  return st == TTS_OK ? n : -st;
+  return num_weights(cfg, tts::glow_encoder_validate, glow_encoder_shapes);
 }
 
 int64_t tts_glow_encoder_weight_numel(const TtsGlowEncoderCfg* cfg, int idx) {
-  int64_t n = -1;
-  guarded([&] {
-    TTS_REQUIRE(cfg, 1, "NULL cfg");
-    tts::glow_encoder_validate(*cfg);
-    auto s = tts::glow_encoder_weight_shapes(*cfg);
-    TTS_REQUIRE(idx >= 0 && idx < (int)s.size(), 1, "weight index out of range");
-    n = s[idx];
-  });
-  return n;
+  return weight_numel(cfg, idx, tts::glow_encoder_validate, glow_encoder_shapes);
 }
 
 int tts_glow_encoder_create(const TtsGlowEncoderCfg* cfg, const float* const* host_weights, int device,
                             void** handle) {
-  return guarded([&] {
-    TTS_REQUIRE(cfg && host_weights && handle, 1, "NULL argument");
-    *handle = nullptr;
-    *handle = new tts::GlowEncoder(*cfg, host_weights, device);
-  });
+  return create<tts::GlowEncoder>(cfg, host_weights, device, handle);
 }
 
-int tts_glow_encoder_destroy(void* handle) {
-  return guarded([&] { delete static_cast<tts::GlowEncoder*>(handle); });
-}
+int tts_glow_encoder_destroy(void* handle) { return destroy<tts::GlowEncoder>(handle); }
 
 int tts_glow_encoder_forward(void* handle, const int64_t* d_tokens, const int64_t* d_lengths, const float* d_g,
                              int B, int T, float* d_x_m, float* d_x_logs, float* d_logw, float* d_x_mask,
@@ -209,18 +220,10 @@ int tts_glow_encoder_forward_profiled(void* handle, const int64_t* d_tokens, con
                                       float* d_x_mask,
                                       void* hip_stream, TtsLaunchRecord* records, int max_records,
                                       int* n_records) {
-  return guarded([&] {
-    TTS_REQUIRE(handle && n_records, 1, "NULL argument");
-    auto* h = static_cast<tts::GlowEncoder*>(handle);
-    auto s = static_cast<hipStream_t>(hip_stream);
-    tts::Profiler prof;
-    {
-      tts::DeviceGuard g(h->device());
-      h->forward(d_tokens, d_lengths, d_g, B, T, d_x_m, d_x_logs, d_logw, d_x_mask, s, &prof);
-      TTS_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    export_records(prof, records, max_records, n_records);
-  });
+  auto body = [&](tts::GlowEncoder& h, hipStream_t s, tts::Profiler* prof) {
+    h.forward(d_tokens, d_lengths, d_g, B, T, d_x_m, d_x_logs, d_logw, d_x_mask, s, prof);
+  };
+  return profiled<tts::GlowEncoder>(handle, hip_stream, records, max_records, n_records, body);
 }
 
 int tts_glow_durations(const float* d_logw, const float* d_x_mask, int B, int T_x, float length_scale,
@@ -278,39 +281,19 @@ int tts_maximum_path(const float* d_value, const float* d_mask, const int64_t* d
 
 // ----------------------------------------------------------------------------- VITS text side
 int tts_vits_text_encoder_num_weights(const TtsVitsTextEncoderCfg* cfg) {
-  int n = -1;
-  int st = guarded([&] {
-    TTS_REQUIRE(cfg, 1, "NULL cfg");
-    tts::vits_text_encoder_validate(*cfg);
-    n = (int)tts::vits_text_encoder_weight_shapes(*cfg).size();
-  });
-  return st == TTS_OK ? n : -st;
+  return num_weights(cfg, tts::vits_text_encoder_validate, tts::vits_text_encoder_weight_shapes);
 }
 
 int64_t tts_vits_text_encoder_weight_numel(const TtsVitsTextEncoderCfg* cfg, int idx) {
-  int64_t n = -1;
-  guarded([&] {
-    TTS_REQUIRE(cfg, 1, "NULL cfg");
-    tts::vits_text_encoder_validate(*cfg);
-    auto s = tts::vits_text_encoder_weight_shapes(*cfg);
-    TTS_REQUIRE(idx >= 0 && idx < (int)s.size(), 1, "weight index out of range");
-    n = s[idx];
-  });
-  return n;
+  return weight_numel(cfg, idx, tts::vits_text_encoder_validate, tts::vits_text_encoder_weight_shapes);
 }
 
 int tts_vits_text_encoder_create(const TtsVitsTextEncoderCfg* cfg, const float* const* host_weights, int device,
                                  void** handle) {
-  return guarded([&] {
-    TTS_REQUIRE(cfg && host_weights && handle, 1, "NULL argument");
-    *handle = nullptr;
-    *handle = new tts::VitsTextEncoder(*cfg, host_weights, device);
-  });
+  return create<tts::VitsTextEncoder>(cfg, host_weights, device, handle);
 }
 
-int tts_vits_text_encoder_destroy(void* handle) {
-  return guarded([&] { delete static_cast<tts::VitsTextEncoder*>(handle); });
-}
+int tts_vits_text_encoder_destroy(void* handle) { return destroy<tts::VitsTextEncoder>(handle); }
 
 int tts_vits_text_encoder_forward(void* handle, const int64_t* d_tokens, const int64_t* d_lengths,
                                   const float* d_lang_emb, int B, int T, float* d_x, float* d_m, float* d_logs,
@@ -326,53 +309,25 @@ int tts_vits_text_encoder_forward_profiled(void* handle, const int64_t* d_tokens
                                            const float* d_lang_emb, int B, int T, float* d_x, float* d_m,
                                            float* d_logs, float* d_x_mask, void* hip_stream,
                                            TtsLaunchRecord* records, int max_records, int* n_records) {
-  return guarded([&] {
-    TTS_REQUIRE(handle && n_records, 1, "NULL argument");
-    auto* h = static_cast<tts::VitsTextEncoder*>(handle);
-    auto s = static_cast<hipStream_t>(hip_stream);
-    tts::Profiler prof;
-    {
-      tts::DeviceGuard g(h->device());
-      h->forward(d_tokens, d_lengths, d_lang_emb, B, T, d_x, d_m, d_logs, d_x_mask, s, &prof);
-      TTS_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    export_records(prof, records, max_records, n_records);
-  });
+  auto body = [&](tts::VitsTextEncoder& h, hipStream_t s, tts::Profiler* prof) {
+    h.forward(d_tokens, d_lengths, d_lang_emb, B, T, d_x, d_m, d_logs, d_x_mask, s, prof);
+  };
+  return profiled<tts::VitsTextEncoder>(handle, hip_stream, records, max_records, n_records, body);
 }
 
 int tts_vits_sdp_num_weights(const TtsVitsSdpCfg* cfg) {
-  int n = -1;
-  int st = guarded([&] {
-    TTS_REQUIRE(cfg, 1, "NULL cfg");
-    tts::vits_sdp_validate(*cfg);
-    n = (int)tts::vits_sdp_weight_shapes(*cfg).size();
-  });
-  return st == TTS_OK ? n : -st;
+  return num_weights(cfg, tts::vits_sdp_validate, tts::vits_sdp_weight_shapes);
 }
 
 int64_t tts_vits_sdp_weight_numel(const TtsVitsSdpCfg* cfg, int idx) {
-  int64_t n = -1;
-  guarded([&] {
-    TTS_REQUIRE(cfg, 1, "NULL cfg");
-    tts::vits_sdp_validate(*cfg);
-    auto s = tts::vits_sdp_weight_shapes(*cfg);
-    TTS_REQUIRE(idx >= 0 && idx < (int)s.size(), 1, "weight index out of range");
-    n = s[idx];
-  });
-  return n;
+  return weight_numel(cfg, idx, tts::vits_sdp_validate, tts::vits_sdp_weight_shapes);
 }
 
 int tts_vits_sdp_create(const TtsVitsSdpCfg* cfg, const float* const* host_weights, int device, void** handle) {
-  return guarded([&] {
-    TTS_REQUIRE(cfg && host_weights && handle, 1, "NULL argument");
-    *handle = nullptr;
-    *handle = new tts::VitsSdp(*cfg, host_weights, device);
-  });
+  return create<tts::VitsSdp>(cfg, host_weights, device, handle);
 }
 
-int tts_vits_sdp_destroy(void* handle) {
-  return guarded([&] { delete static_cast<tts::VitsSdp*>(handle); });
-}
+int tts_vits_sdp_destroy(void* handle) { return destroy<tts::VitsSdp>(handle); }
 
 int tts_vits_sdp_reverse(void* handle, const float* d_x, const float* d_x_mask, const float* d_g,
                          const float* d_lang_emb, const float* d_noise, float noise_scale, int B, int T,
@@ -388,53 +343,25 @@ int tts_vits_sdp_reverse_profiled(void* handle, const float* d_x, const float* d
                                   const float* d_lang_emb, const float* d_noise, float noise_scale, int B, int T,
                                   float* d_logw, void* hip_stream, TtsLaunchRecord* records, int max_records,
                                   int* n_records) {
-  return guarded([&] {
-    TTS_REQUIRE(handle && n_records, 1, "NULL argument");
-    auto* h = static_cast<tts::VitsSdp*>(handle);
-    auto s = static_cast<hipStream_t>(hip_stream);
-    tts::Profiler prof;
-    {
-      tts::DeviceGuard g(h->device());
-      h->reverse(d_x, d_x_mask, d_g, d_lang_emb, d_noise, noise_scale, B, T, d_logw, s, &prof);
-      TTS_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    export_records(prof, records, max_records, n_records);
-  });
+  auto body = [&](tts::VitsSdp& h, hipStream_t s, tts::Profiler* prof) {
+    h.reverse(d_x, d_x_mask, d_g, d_lang_emb, d_noise, noise_scale, B, T, d_logw, s, prof);
+  };
+  return profiled<tts::VitsSdp>(handle, hip_stream, records, max_records, n_records, body);
 }
 
 int tts_vits_dp_num_weights(const TtsVitsDpCfg* cfg) {
-  int n = -1;
-  int st = guarded([&] {
-    TTS_REQUIRE(cfg, 1, "NULL cfg");
-    tts::vits_dp_validate(*cfg);
-    n = (int)tts::vits_dp_weight_shapes(*cfg).size();
-  });
-  return st == TTS_OK ? n : -st;
+  return num_weights(cfg, tts::vits_dp_validate, tts::vits_dp_weight_shapes);
 }
 
 int64_t tts_vits_dp_weight_numel(const TtsVitsDpCfg* cfg, int idx) {
-  int64_t n = -1;
-  guarded([&] {
-    TTS_REQUIRE(cfg, 1, "NULL cfg");
-    tts::vits_dp_validate(*cfg);
-    auto s = tts::vits_dp_weight_shapes(*cfg);
-    TTS_REQUIRE(idx >= 0 && idx < (int)s.size(), 1, "weight index out of range");
-    n = s[idx];
-  });
-  return n;
+  return weight_numel(cfg, idx, tts::vits_dp_validate, tts::vits_dp_weight_shapes);
 }
 
 int tts_vits_dp_create(const TtsVitsDpCfg* cfg, const float* const* host_weights, int device, void** handle) {
-  return guarded([&] {
-    TTS_REQUIRE(cfg && host_weights && handle, 1, "NULL argument");
-    *handle = nullptr;
-    *handle = new tts::VitsDp(*cfg, host_weights, device);
-  });
+  return create<tts::VitsDp>(cfg, host_weights, device, handle);
 }
 
-int tts_vits_dp_destroy(void* handle) {
-  return guarded([&] { delete static_cast<tts::VitsDp*>(handle); });
-}
+int tts_vits_dp_destroy(void* handle) { return destroy<tts::VitsDp>(handle); }
 
 int tts_vits_dp_forward(void* handle, const float* d_x, const float* d_x_mask, const float* d_g,
                         const float* d_lang_emb, int B, int T, float* d_logw, void* hip_stream) {
@@ -448,18 +375,10 @@ int tts_vits_dp_forward(void* handle, const float* d_x, const float* d_x_mask, c
 int tts_vits_dp_forward_profiled(void* handle, const float* d_x, const float* d_x_mask, const float* d_g,
                                  const float* d_lang_emb, int B, int T, float* d_logw, void* hip_stream,
                                  TtsLaunchRecord* records, int max_records, int* n_records) {
-  return guarded([&] {
-    TTS_REQUIRE(handle && n_records, 1, "NULL argument");
-    auto* h = static_cast<tts::VitsDp*>(handle);
-    auto s = static_cast<hipStream_t>(hip_stream);
-    tts::Profiler prof;
-    {
-      tts::DeviceGuard g(h->device());
-      h->forward(d_x, d_x_mask, d_g, d_lang_emb, B, T, d_logw, s, &prof);
-      TTS_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    export_records(prof, records, max_records, n_records);
-  });
+  auto body = [&](tts::VitsDp& h, hipStream_t s, tts::Profiler* prof) {
+    h.forward(d_x, d_x_mask, d_g, d_lang_emb, B, T, d_logw, s, prof);
+  };
+  return profiled<tts::VitsDp>(handle, hip_stream, records, max_records, n_records, body);
 }
 
 int tts_vits_durations(const float* d_logw, const float* d_x_mask, int B, int T_x, float length_scale,
@@ -584,39 +503,19 @@ int tts_wav_to_int16(const float* d_wav, int B, int64_t n, const int64_t* d_leng
 
 // ----------------------------------------------------------------------------- Glow decoder
 int tts_glow_decoder_num_weights(const TtsGlowDecoderCfg* cfg) {
-  int n = -1;
-  int st = guarded([&] {
-    TTS_REQUIRE(cfg, 1, "NULL cfg");
-    tts::glow_validate(*cfg);
-    n = (int)tts::glow_weight_shapes(*cfg).size();
-  });
-  return st == TTS_OK ? n : -st;
+  return num_weights(cfg, tts::glow_validate, tts::glow_weight_shapes);
 }
 
 int64_t tts_glow_decoder_weight_numel(const TtsGlowDecoderCfg* cfg, int idx) {
-  int64_t n = -1;
-  guarded([&] {
-    TTS_REQUIRE(cfg, 1, "NULL cfg");
-    tts::glow_validate(*cfg);
-    auto s = tts::glow_weight_shapes(*cfg);
-    TTS_REQUIRE(idx >= 0 && idx < (int)s.size(), 1, "weight index out of range");
-    n = s[idx];
-  });
-  return n;
+  return weight_numel(cfg, idx, tts::glow_validate, tts::glow_weight_shapes);
 }
 
 int tts_glow_decoder_create(const TtsGlowDecoderCfg* cfg, const float* const* host_weights,
                             int device, void** handle) {
-  return guarded([&] {
-    TTS_REQUIRE(cfg && host_weights && handle, 1, "NULL argument");
-    *handle = nullptr;
-    *handle = new tts::GlowDecoder(*cfg, host_weights, device);
-  });
+  return create<tts::GlowDecoder>(cfg, host_weights, device, handle);
 }
 
-int tts_glow_decoder_destroy(void* handle) {
-  return guarded([&] { delete static_cast<tts::GlowDecoder*>(handle); });
-}
+int tts_glow_decoder_destroy(void* handle) { return destroy<tts::GlowDecoder>(handle); }
 
 int tts_glow_decoder_forward(void* handle, const float* d_x, const float* d_mask, const float* d_g, int B,
                              int C, int T, int reverse, float* d_y, float* d_logdet, void* hip_stream) {
@@ -632,56 +531,28 @@ int tts_glow_decoder_forward(void* handle, const float* d_x, const float* d_mask
 int tts_glow_decoder_forward_profiled(void* handle, const float* d_x, const float* d_mask, const float* d_g,
                                       int B, int C, int T, int reverse, float* d_y, float* d_logdet,
                                       void* hip_stream, TtsLaunchRecord* records, int max_records, int* n_records) {
-  return guarded([&] {
-    TTS_REQUIRE(handle && n_records, 1, "NULL argument");
+  auto body = [&](tts::GlowDecoder& h, hipStream_t s, tts::Profiler* prof) {
     TTS_REQUIRE(reverse == 0 || reverse == 1, 1, "reverse must be 0 or 1");
-    auto* h = static_cast<tts::GlowDecoder*>(handle);
-    auto s = static_cast<hipStream_t>(hip_stream);
-    tts::Profiler prof;
-    {
-      tts::DeviceGuard g(h->device());
-      if (reverse) h->reverse(d_x, d_mask, d_g, B, C, T, d_y, s, &prof);
-      else h->forward(d_x, d_mask, d_g, B, C, T, d_y, d_logdet, s, &prof);
-      TTS_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    export_records(prof, records, max_records, n_records);
-  });
+    if (reverse) h.reverse(d_x, d_mask, d_g, B, C, T, d_y, s, prof);
+    else h.forward(d_x, d_mask, d_g, B, C, T, d_y, d_logdet, s, prof);
+  };
+  return profiled<tts::GlowDecoder>(handle, hip_stream, records, max_records, n_records, body);
 }
 
 // ----------------------------------------------------------------------------- VITS flow
 int tts_vits_flow_num_weights(const TtsVitsFlowCfg* cfg) {
-  int n = -1;
-  int st = guarded([&] {
-    TTS_REQUIRE(cfg, 1, "NULL cfg");
-    tts::vits_flow_validate(*cfg);
-    n = (int)tts::vits_flow_weight_shapes(*cfg).size();
-  });
-  return st == TTS_OK ? n : -st;
+  return num_weights(cfg, tts::vits_flow_validate, tts::vits_flow_weight_shapes);
 }
 
 int64_t tts_vits_flow_weight_numel(const TtsVitsFlowCfg* cfg, int idx) {
-  int64_t n = -1;
-  guarded([&] {
-    TTS_REQUIRE(cfg, 1, "NULL cfg");
-    tts::vits_flow_validate(*cfg);
-    auto s = tts::vits_flow_weight_shapes(*cfg);
-    TTS_REQUIRE(idx >= 0 && idx < (int)s.size(), 1, "weight index out of range");
-    n = s[idx];
-  });
-  return n;
+  return weight_numel(cfg, idx, tts::vits_flow_validate, tts::vits_flow_weight_shapes);
 }
 
 int tts_vits_flow_create(const TtsVitsFlowCfg* cfg, const float* const* host_weights, int device, void** handle) {
-  return guarded([&] {
-    TTS_REQUIRE(cfg && host_weights && handle, 1, "NULL argument");
-    *handle = nullptr;
-    *handle = new tts::VitsFlow(*cfg, host_weights, device);
-  });
+  return create<tts::VitsFlow>(cfg, host_weights, device, handle);
 }
 
-int tts_vits_flow_destroy(void* handle) {
-  return guarded([&] { delete static_cast<tts::VitsFlow*>(handle); });
-}
+int tts_vits_flow_destroy(void* handle) { return destroy<tts::VitsFlow>(handle); }
 
 int tts_vits_flow_forward(void* handle, const float* d_x, const float* d_mask, const float* d_g, int B, int C,
                           int T, int reverse, float* d_y, void* hip_stream) {
@@ -697,57 +568,29 @@ int tts_vits_flow_forward(void* handle, const float* d_x, const float* d_mask, c
 int tts_vits_flow_forward_profiled(void* handle, const float* d_x, const float* d_mask, const float* d_g, int B,
                                    int C, int T, int reverse, float* d_y, void* hip_stream,
                                    TtsLaunchRecord* records, int max_records, int* n_records) {
-  return guarded([&] {
-    TTS_REQUIRE(handle && n_records, 1, "NULL argument");
+  auto body = [&](tts::VitsFlow& h, hipStream_t s, tts::Profiler* prof) {
     TTS_REQUIRE(reverse == 0 || reverse == 1, 1, "reverse must be 0 or 1");
-    auto* h = static_cast<tts::VitsFlow*>(handle);
-    auto s = static_cast<hipStream_t>(hip_stream);
-    tts::Profiler prof;
-    {
-      tts::DeviceGuard g(h->device());
-      if (reverse) h->reverse(d_x, d_mask, d_g, B, C, T, d_y, s, &prof);
-      else h->forward(d_x, d_mask, d_g, B, C, T, d_y, s, &prof);
-      TTS_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    export_records(prof, records, max_records, n_records);
-  });
+    if (reverse) h.reverse(d_x, d_mask, d_g, B, C, T, d_y, s, prof);
+    else h.forward(d_x, d_mask, d_g, B, C, T, d_y, s, prof);
+  };
+  return profiled<tts::VitsFlow>(handle, hip_stream, records, max_records, n_records, body);
 }
 
 // ----------------------------------------------------------------------------- VITS posterior encoder
 int tts_vits_posterior_num_weights(const TtsVitsPosteriorCfg* cfg) {
-  int n = -1;
-  int st = guarded([&] {
-    TTS_REQUIRE(cfg, 1, "NULL cfg");
-    tts::vits_posterior_validate(*cfg);
-    n = (int)tts::vits_posterior_weight_shapes(*cfg).size();
-  });
-  return st == TTS_OK ? n : -st;
+  return num_weights(cfg, tts::vits_posterior_validate, tts::vits_posterior_weight_shapes);
 }
 
 int64_t tts_vits_posterior_weight_numel(const TtsVitsPosteriorCfg* cfg, int idx) {
-  int64_t n = -1;
-  guarded([&] {
-    TTS_REQUIRE(cfg, 1, "NULL cfg");
-    tts::vits_posterior_validate(*cfg);
-    auto s = tts::vits_posterior_weight_shapes(*cfg);
-    TTS_REQUIRE(idx >= 0 && idx < (int)s.size(), 1, "weight index out of range");
-    n = s[idx];
-  });
-  return n;
+  return weight_numel(cfg, idx, tts::vits_posterior_validate, tts::vits_posterior_weight_shapes);
 }
 
 int tts_vits_posterior_create(const TtsVitsPosteriorCfg* cfg, const float* const* host_weights, int device,
                               void** handle) {
-  return guarded([&] {
-    TTS_REQUIRE(cfg && host_weights && handle, 1, "NULL argument");
-    *handle = nullptr;
-    *handle = new tts::VitsPosterior(*cfg, host_weights, device);
-  });
+  return create<tts::VitsPosterior>(cfg, host_weights, device, handle);
 }
 
-int tts_vits_posterior_destroy(void* handle) {
-  return guarded([&] { delete static_cast<tts::VitsPosterior*>(handle); });
-}
+int tts_vits_posterior_destroy(void* handle) { return destroy<tts::VitsPosterior>(handle); }
 
 int tts_vits_posterior_forward(void* handle, const float* d_x, const float* d_mask, const float* d_g,
                                const float* d_eps, int B, int C, int T, float* d_z, float* d_m, float* d_logs,
@@ -763,32 +606,18 @@ int tts_vits_posterior_forward_profiled(void* handle, const float* d_x, const fl
                                         const float* d_eps, int B, int C, int T, float* d_z, float* d_m,
                                         float* d_logs, void* hip_stream, TtsLaunchRecord* records,
                                         int max_records, int* n_records) {
-  return guarded([&] {
-    TTS_REQUIRE(handle && n_records, 1, "NULL argument");
-    auto* h = static_cast<tts::VitsPosterior*>(handle);
-    auto s = static_cast<hipStream_t>(hip_stream);
-    tts::Profiler prof;
-    {
-      tts::DeviceGuard g(h->device());
-      h->forward(d_x, d_mask, d_g, d_eps, B, C, T, d_z, d_m, d_logs, s, &prof);
-      TTS_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    export_records(prof, records, max_records, n_records);
-  });
+  auto body = [&](tts::VitsPosterior& h, hipStream_t s, tts::Profiler* prof) {
+    h.forward(d_x, d_mask, d_g, d_eps, B, C, T, d_z, d_m, d_logs, s, prof);
+  };
+  return profiled<tts::VitsPosterior>(handle, hip_stream, records, max_records, n_records, body);
 }
 
 // ----------------------------------------------------------------------------- linear spectrogram
 int tts_stft_create(const TtsStftCfg* cfg, const float* h_window, int device, void** handle) {
-  return guarded([&] {
-    TTS_REQUIRE(cfg && h_window && handle, 1, "NULL argument");
-    *handle = nullptr;
-    *handle = new tts::Stft(*cfg, h_window, device);
-  });
+  return create<tts::Stft>(cfg, h_window, device, handle);
 }
 
-int tts_stft_destroy(void* handle) {
-  return guarded([&] { delete static_cast<tts::Stft*>(handle); });
-}
+int tts_stft_destroy(void* handle) { return destroy<tts::Stft>(handle); }
 
 int tts_stft_num_frames(const TtsStftCfg* cfg, int64_t N) {
   int n = -1;
@@ -810,18 +639,10 @@ int tts_stft_forward(void* handle, const float* d_wav, int B, int64_t N, int64_t
 int tts_stft_forward_profiled(void* handle, const float* d_wav, int B, int64_t N, int64_t wav_bstride,
                               float* d_spec, void* hip_stream, TtsLaunchRecord* records, int max_records,
                               int* n_records) {
-  return guarded([&] {
-    TTS_REQUIRE(handle && n_records, 1, "NULL argument");
-    auto* h = static_cast<tts::Stft*>(handle);
-    auto s = static_cast<hipStream_t>(hip_stream);
-    tts::Profiler prof;
-    {
-      tts::DeviceGuard g(h->device());
-      h->forward(d_wav, B, N, wav_bstride, d_spec, s, &prof);
-      TTS_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    export_records(prof, records, max_records, n_records);
-  });
+  auto body = [&](tts::Stft& h, hipStream_t s, tts::Profiler* prof) {
+    h.forward(d_wav, B, N, wav_bstride, d_spec, s, prof);
+  };
+  return profiled<tts::Stft>(handle, hip_stream, records, max_records, n_records, body);
 }
 
 // ----------------------------------------------------------------------------- single ops
@@ -842,9 +663,9 @@ static void op_conv1d_impl(const TtsConv1dDesc* d, const float* d_x, const float
   const int w_exp = tts::pack_conv(mode, h_w, d->Cout, d->Cin, d->K, t, packed.data());
   std::vector<float> bias((size_t)tts::ceil_div(d->Cout, t.BM) * t.BM, 0.f);
   std::memcpy(bias.data(), h_b, sizeof(float) * d->Cout);
-  TmpDev w(packed.data(), packed.size()), b(bias.data(), bias.size());
+  const tts::DeviceBuffer w = to_device(packed.data(), packed.size()), b = to_device(bias.data(), bias.size());
   tts::Conv1dArgs a{};
-  a.x = d_x; a.w = w.p; a.bias = b.p; a.res = d_res; a.y = d_y; a.z = d_z; a.cvec = nullptr;
+  a.x = d_x; a.w = w.as<>(); a.bias = b.as<>(); a.res = d_res; a.y = d_y; a.z = d_z; a.cvec = nullptr;
   a.Cin = d->Cin; a.Cout = d->Cout; a.Tin = d->Tin; a.Tout = d->Tin + 2 * d->rep_pad;
   a.dil = d->dil; a.pad = d->dil * (d->K - 1) / 2; a.rep_pad = d->rep_pad;
   a.n_chunks = tts::ceil_div(d->Cin, t.CK);
@@ -852,12 +673,12 @@ static void op_conv1d_impl(const TtsConv1dDesc* d, const float* d_x, const float
   a.w_exp = w_exp;
   auto s = static_cast<hipStream_t>(hip_stream);
   // fp16 hi/lo mode: the input's max-abs statistic (the executors get it from the producer)
-  std::unique_ptr<TmpDev> slots;
+  tts::DeviceBuffer slots;
   if (mode == tts::MATH_FP32_F16X3) {
-    slots.reset(new TmpDev(nullptr, (size_t)d->B * 64));
-    TTS_HIP_CHECK(hipMemsetAsync(slots->p, 0, (size_t)d->B * 64 * sizeof(float), s));
-    tts::launch_amax(d_x, (int64_t)d->Cin * d->Tin, d->B, reinterpret_cast<unsigned*>(slots->p), s);
-    a.amax_in = reinterpret_cast<const unsigned*>(slots->p);
+    slots = to_device(nullptr, (size_t)d->B * 64);
+    TTS_HIP_CHECK(hipMemsetAsync(slots.as<>(), 0, (size_t)d->B * 64 * sizeof(float), s));
+    tts::launch_amax(d_x, (int64_t)d->Cin * d->Tin, d->B, slots.as<unsigned>(), s);
+    a.amax_in = slots.as<unsigned>();
   }
   if (reps <= 0) {
     tts::launch_conv(mode, a, d->B, d->K, tile, s);
@@ -916,18 +737,18 @@ int tts_op_conv_transpose1d(const float* d_x, int B, int Cin, int Tin, const flo
       std::vector<float> bias((size_t)tts::ceil_div(stride * Cout, t.BM) * t.BM, 0.f);
       for (int co = 0; co < Cout; ++co)
         for (int ph = 0; ph < stride; ++ph) bias[(size_t)co * stride + ph] = h_b[co];
-      TmpDev w(packed.data(), packed.size()), b(bias.data(), bias.size());
+      const tts::DeviceBuffer w = to_device(packed.data(), packed.size()), b = to_device(bias.data(), bias.size());
       tts::Conv1dArgs a{};
-      a.x = d_x; a.w = w.p; a.bias = b.p; a.y = d_y;
+      a.x = d_x; a.w = w.as<>(); a.bias = b.as<>(); a.y = d_y;
       a.Cin = Cin; a.Cout = stride * Cout; a.Tin = Tin; a.Tout = Tin + 1;
       a.dil = 1; a.pad = 1; a.n_chunks = tts::ceil_div(Cin, t.CK);
       a.in_slope = in_slope; a.out_slope = 1.f; a.zdiv = 1.f; a.w_exp = w_exp; a.ups = stride;
-      std::unique_ptr<TmpDev> slots;
+      tts::DeviceBuffer slots;
       if (math_mode == tts::MATH_FP32_F16X3) {
-        slots.reset(new TmpDev(nullptr, (size_t)B * 64));
-        TTS_HIP_CHECK(hipMemsetAsync(slots->p, 0, (size_t)B * 64 * sizeof(float), s));
-        tts::launch_amax(d_x, (int64_t)Cin * Tin, B, reinterpret_cast<unsigned*>(slots->p), s);
-        a.amax_in = reinterpret_cast<const unsigned*>(slots->p);
+        slots = to_device(nullptr, (size_t)B * 64);
+        TTS_HIP_CHECK(hipMemsetAsync(slots.as<>(), 0, (size_t)B * 64 * sizeof(float), s));
+        tts::launch_amax(d_x, (int64_t)Cin * Tin, B, slots.as<unsigned>(), s);
+        a.amax_in = slots.as<unsigned>();
       }
       tts::launch_conv(math_mode, a, B, 2, tile, s);
       TTS_HIP_CHECK(hipStreamSynchronize(s));
@@ -939,9 +760,9 @@ int tts_op_conv_transpose1d(const float* d_x, int B, int Cin, int Tin, const flo
     tts::pack_convT(h_w, Cin, Cout, stride, t, packed.data());
     std::vector<float> bias((size_t)tts::ceil_div(Cout, t.BM) * t.BM, 0.f);
     std::memcpy(bias.data(), h_b, sizeof(float) * Cout);
-    TmpDev w(packed.data(), packed.size()), b(bias.data(), bias.size());
+    const tts::DeviceBuffer w = to_device(packed.data(), packed.size()), b = to_device(bias.data(), bias.size());
     tts::ConvTArgs a{};
-    a.x = d_x; a.w = w.p; a.bias = b.p; a.y = d_y;
+    a.x = d_x; a.w = w.as<>(); a.bias = b.as<>(); a.y = d_y;
     a.Cin = Cin; a.Cout = Cout; a.Tin = Tin; a.n_chunks = tts::ceil_div(Cin, t.CK); a.in_slope = in_slope;
     tts::launch_convT(a, B, stride, tile, s);
     TTS_HIP_CHECK(hipStreamSynchronize(s));
@@ -953,9 +774,9 @@ int tts_op_conv_post(const float* d_z, int B, int Cin, int T, const float* h_w, 
   return guarded([&] {
     TTS_REQUIRE(d_z && h_w && d_y, 1, "NULL argument");
     TTS_REQUIRE(B >= 1 && Cin >= 1 && T >= 1, 1, "bad conv_post shape");
-    TmpDev w(h_w, (size_t)Cin * 7);
+    const tts::DeviceBuffer w = to_device(h_w, (size_t)Cin * 7);
     tts::PostArgs a{};
-    a.z = d_z; a.w = w.p; a.bias = h_b ? h_b[0] : 0.f; a.y = d_y; a.Cin = Cin; a.T = T; a.in_slope = in_slope;
+    a.z = d_z; a.w = w.as<>(); a.bias = h_b ? h_b[0] : 0.f; a.y = d_y; a.Cin = Cin; a.T = T; a.in_slope = in_slope;
     auto s = static_cast<hipStream_t>(hip_stream);
     tts::launch_conv_post(a, B, s);
     TTS_HIP_CHECK(hipStreamSynchronize(s));
@@ -964,36 +785,18 @@ int tts_op_conv_post(const float* d_z, int B, int Cin, int T, const float* h_w, 
 
 // ----------------------------------------------------------------------------- MelGAN family
 int tts_melgan_num_weights(const TtsMelganCfg* cfg) {
-  int n = -1;
-  int st = guarded([&] {
-    TTS_REQUIRE(cfg, 1, "NULL cfg");
-    n = (int)tts::melgan_weight_shapes(*cfg).size();
-  });
-  return st == TTS_OK ? n : -st;
+  return num_weights(cfg, [](const TtsMelganCfg&) {}, tts::melgan_weight_shapes);
 }
 
 int64_t tts_melgan_weight_numel(const TtsMelganCfg* cfg, int idx) {
-  int64_t n = -1;
-  guarded([&] {
-    TTS_REQUIRE(cfg, 1, "NULL cfg");
-    auto s = tts::melgan_weight_shapes(*cfg);
-    TTS_REQUIRE(idx >= 0 && idx < (int)s.size(), 1, "weight index out of range");
-    n = s[idx];
-  });
-  return n;
+  return weight_numel(cfg, idx, [](const TtsMelganCfg&) {}, tts::melgan_weight_shapes);
 }
 
 int tts_melgan_create(const TtsMelganCfg* cfg, const float* const* host_weights, int device, void** handle) {
-  return guarded([&] {
-    TTS_REQUIRE(cfg && host_weights && handle, 1, "NULL argument");
-    *handle = nullptr;
-    *handle = new tts::Melgan(*cfg, host_weights, device);
-  });
+  return create<tts::Melgan>(cfg, host_weights, device, handle);
 }
 
-int tts_melgan_destroy(void* handle) {
-  return guarded([&] { delete static_cast<tts::Melgan*>(handle); });
-}
+int tts_melgan_destroy(void* handle) { return destroy<tts::Melgan>(handle); }
 
 int64_t tts_melgan_output_length(const void* handle, int T, int pad, int synth) {
   int64_t n = -1;
@@ -1024,18 +827,10 @@ int tts_melgan_forward(void* handle, const float* d_mel, int B, int C, int T, in
 int tts_melgan_forward_profiled(void* handle, const float* d_mel, int B, int C, int T, int pad, int synth,
                                 float* d_out, void* hip_stream, TtsLaunchRecord* records, int max_records,
                                 int* n_records) {
-  return guarded([&] {
-    TTS_REQUIRE(handle && n_records, 1, "NULL argument");
-    auto* h = static_cast<tts::Melgan*>(handle);
-    auto s = static_cast<hipStream_t>(hip_stream);
-    tts::Profiler prof;
-    {
-      tts::DeviceGuard g(h->device());
-      h->forward(d_mel, B, C, T, pad, synth, d_out, s, &prof);
-      TTS_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    export_records(prof, records, max_records, n_records);
-  });
+  auto body = [&](tts::Melgan& h, hipStream_t s, tts::Profiler* prof) {
+    h.forward(d_mel, B, C, T, pad, synth, d_out, s, prof);
+  };
+  return profiled<tts::Melgan>(handle, hip_stream, records, max_records, n_records, body);
 }
 
 int tts_op_melgan_block(const float* d_x, int B, int C, int L, int dilation, const float* h_w1, const float* h_b1,
@@ -1052,9 +847,10 @@ int tts_op_melgan_block(const float* d_x, int B, int C, int L, int dilation, con
     std::vector<float> a1((size_t)n1 / 2), a2((size_t)n2 / 2), bias1(nb), bias2(nb);
     tts::pack_melgan_block(mode, h_w1, h_b1, h_w2, h_b2, h_ws, h_bs, C, reinterpret_cast<uint16_t*>(a1.data()),
                            reinterpret_cast<uint16_t*>(a2.data()), bias1.data(), bias2.data());
-    TmpDev da1(a1.data(), a1.size()), da2(a2.data(), a2.size()), db1(bias1.data(), nb), db2(bias2.data(), nb);
+    const tts::DeviceBuffer da1 = to_device(a1.data(), a1.size()), da2 = to_device(a2.data(), a2.size());
+    const tts::DeviceBuffer db1 = to_device(bias1.data(), nb), db2 = to_device(bias2.data(), nb);
     tts::MelganBlockArgs a{};
-    a.x = d_x; a.y = d_out; a.a1 = da1.p; a.a2 = da2.p; a.bias1 = db1.p; a.bias2 = db2.p;
+    a.x = d_x; a.y = d_out; a.a1 = da1.as<>(); a.a2 = da2.as<>(); a.bias1 = db1.as<>(); a.bias2 = db2.as<>();
     a.a1_bytes = (unsigned)(n1 * 2); a.a2_bytes = (unsigned)(n2 * 2);
     a.C = C; a.L = L; a.dil = dilation;
     auto s = static_cast<hipStream_t>(hip_stream);
@@ -1085,38 +881,18 @@ int tts_op_mha(const float* d_qkv, const int64_t* d_key_lengths, int B, int E, i
 int tts_op_mha_tile(void) { return tts::kMhaTile; }
 
 int tts_forward_tts_num_weights(const TtsForwardTtsCfg* cfg) {
-  int n = -1;
-  int st = guarded([&] {
-    TTS_REQUIRE(cfg, 1, "NULL cfg");
-    tts::forward_tts_validate(*cfg);
-    n = (int)tts::forward_tts_weight_shapes(*cfg).size();
-  });
-  return st == TTS_OK ? n : -st;
+  return num_weights(cfg, tts::forward_tts_validate, tts::forward_tts_weight_shapes);
 }
 
 int64_t tts_forward_tts_weight_numel(const TtsForwardTtsCfg* cfg, int idx) {
-  int64_t n = -1;
-  guarded([&] {
-    TTS_REQUIRE(cfg, 1, "NULL cfg");
-    tts::forward_tts_validate(*cfg);
-    auto s = tts::forward_tts_weight_shapes(*cfg);
-    TTS_REQUIRE(idx >= 0 && idx < (int)s.size(), 1, "weight index out of range");
-    n = s[idx];
-  });
-  return n;
+  return weight_numel(cfg, idx, tts::forward_tts_validate, tts::forward_tts_weight_shapes);
 }
 
 int tts_forward_tts_create(const TtsForwardTtsCfg* cfg, const float* const* host_weights, int device, void** handle) {
-  return guarded([&] {
-    TTS_REQUIRE(cfg && host_weights && handle, 1, "NULL argument");
-    *handle = nullptr;
-    *handle = new tts::ForwardTts(*cfg, host_weights, device);
-  });
+  return create<tts::ForwardTts>(cfg, host_weights, device, handle);
 }
 
-int tts_forward_tts_destroy(void* handle) {
-  return guarded([&] { delete static_cast<tts::ForwardTts*>(handle); });
-}
+int tts_forward_tts_destroy(void* handle) { return destroy<tts::ForwardTts>(handle); }
 
 int tts_forward_tts_encode(void* handle, const int64_t* d_tokens, const int64_t* d_x_lengths,
                            const int64_t* d_speaker_ids, const float* d_given_durations, int B, int T_en,
@@ -1135,19 +911,11 @@ int tts_forward_tts_encode_profiled(void* handle, const int64_t* d_tokens, const
                                     float length_scale, float* d_o_en, float* d_x_mask, float* d_durations_log,
                                     float* d_pitch, float* d_durations, int64_t* d_y_lengths, void* hip_stream,
                                     TtsLaunchRecord* records, int max_records, int* n_records) {
-  return guarded([&] {
-    TTS_REQUIRE(handle && n_records, 1, "NULL argument");
-    auto* h = static_cast<tts::ForwardTts*>(handle);
-    auto s = static_cast<hipStream_t>(hip_stream);
-    tts::Profiler prof;
-    {
-      tts::DeviceGuard g(h->device());
-      h->encode(d_tokens, d_x_lengths, d_speaker_ids, d_given_durations, B, T_en, length_scale, d_o_en, d_x_mask,
-                d_durations_log, d_pitch, d_durations, d_y_lengths, s, &prof);
-      TTS_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    export_records(prof, records, max_records, n_records);
-  });
+  auto body = [&](tts::ForwardTts& h, hipStream_t s, tts::Profiler* prof) {
+    h.encode(d_tokens, d_x_lengths, d_speaker_ids, d_given_durations, B, T_en, length_scale, d_o_en, d_x_mask,
+             d_durations_log, d_pitch, d_durations, d_y_lengths, s, prof);
+  };
+  return profiled<tts::ForwardTts>(handle, hip_stream, records, max_records, n_records, body);
 }
 
 int tts_forward_tts_decode(void* handle, const float* d_o_en, const float* d_durations, const float* d_x_mask,
@@ -1165,19 +933,11 @@ int tts_forward_tts_decode_profiled(void* handle, const float* d_o_en, const flo
                                     const int64_t* d_y_lengths, int B, int T_en, int T_de, int mask_decoder_keys,
                                     float* d_out, float* d_attn, float* d_y_mask, void* hip_stream,
                                     TtsLaunchRecord* records, int max_records, int* n_records) {
-  return guarded([&] {
-    TTS_REQUIRE(handle && n_records, 1, "NULL argument");
-    auto* h = static_cast<tts::ForwardTts*>(handle);
-    auto s = static_cast<hipStream_t>(hip_stream);
-    tts::Profiler prof;
-    {
-      tts::DeviceGuard g(h->device());
-      h->decode(d_o_en, d_durations, d_x_mask, d_y_lengths, B, T_en, T_de, mask_decoder_keys != 0, d_out, d_attn,
-                d_y_mask, s, &prof);
-      TTS_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    export_records(prof, records, max_records, n_records);
-  });
+  auto body = [&](tts::ForwardTts& h, hipStream_t s, tts::Profiler* prof) {
+    h.decode(d_o_en, d_durations, d_x_mask, d_y_lengths, B, T_en, T_de, mask_decoder_keys != 0, d_out, d_attn,
+             d_y_mask, s, prof);
+  };
+  return profiled<tts::ForwardTts>(handle, hip_stream, records, max_records, n_records, body);
 }
 
 int tts_forward_tts_block(void* handle, int decoder, const float* d_x, const int64_t* d_key_lengths, int B, int T,

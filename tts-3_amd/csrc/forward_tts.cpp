@@ -17,7 +17,6 @@
 #include "forward_tts.hpp"
 
 #include <cmath>
-#include <cstring>
 #include <string>
 
 #include "fft_attn.hpp"
@@ -94,41 +93,26 @@ ForwardTts::ForwardTts(const TtsForwardTtsCfg& cfg, const float* const* hw, int 
   for (size_t i = 0; i < shapes.size(); ++i)
     TTS_REQUIRE(hw[i] != nullptr, 1, "weight pointer " + std::to_string(i) + " is NULL");
   const int H = cfg_.hidden_channels;
-  std::vector<float> host;
-  std::vector<std::pair<size_t, float**>> fix;
-  auto align = [](size_t n) { return (n + 63) & ~size_t(63); };
-  auto put = [&](const float* src, size_t n, float** dst) {
-    const size_t off = host.size();
-    host.resize(off + align(n), 0.f);
-    std::memcpy(host.data() + off, src, n * sizeof(float));
-    fix.push_back({off, dst});
-  };
+  HostArena arena;
   // text: the short-batch tile of the Glow encoder; frames: the tile table's choice for the shape
   auto put_conv = [&](Conv& cv, const float* w, const float* b, int Cout, int Cin, int K, int mode, bool frames,
                       float wscale) {
     cv.Cin = Cin; cv.Cout = Cout; cv.K = K;
     cv.tile = frames ? conv_tile_for(mode, Cout, K, Cin, 1, false) : 16;
-    const ConvTile t = conv_tile(mode, cv.tile);
-    cv.n_chunks = ceil_div(Cin, t.CK);
-    std::vector<float> ws;
+    std::vector<float> ws, bs;
     if (wscale != 1.f) {
       ws.assign(w, w + (size_t)Cout * Cin * K);
+      bs.assign(b, b + Cout);
       for (float& v : ws) v *= wscale;
+      for (float& v : bs) v *= wscale;
       w = ws.data();
+      b = bs.data();
     }
-    const size_t n = packed_conv_numel(mode, Cout, Cin, K, t);
-    const size_t off = host.size();
-    host.resize(off + align(n), 0.f);
-    TTS_REQUIRE(pack_conv(mode, w, Cout, Cin, K, t, host.data() + off) == 0, 3, "ForwardTTS: scaled packing unsupported");
-    fix.push_back({off, &cv.w});
-    const size_t nb = (size_t)ceil_div(Cout, t.BM) * t.BM;
-    const size_t offb = host.size();
-    host.resize(offb + align(nb), 0.f);
-    for (int i = 0; i < Cout; ++i) host[offb + i] = b[i] * wscale;
-    fix.push_back({offb, &cv.b});
+    TTS_REQUIRE(arena.put_conv(cv, mode, conv_tile(mode, cv.tile), w, b) == 0, 3,
+                "ForwardTTS: scaled packing unsupported");
   };
   size_t wi = 0;
-  put(hw[wi++], (size_t)cfg_.num_chars * H, &emb_);
+  arena.put(hw[wi++], (size_t)cfg_.num_chars * H, &emb_);
   auto put_block = [&](std::vector<Layer>& layers, int n, int F, int mode, bool frames) {
     layers.resize(n);
     for (Layer& L : layers) {
@@ -136,13 +120,13 @@ ForwardTts::ForwardTts(const TtsForwardTtsCfg& cfg, const float* const* hw, int 
       put_conv(L.o, hw[wi + 2], hw[wi + 3], H, H, 1, mode, frames, 2.f);
       put_conv(L.ffn1, hw[wi + 4], hw[wi + 5], F, H, kFftKernel, mode, frames, 1.f);
       put_conv(L.ffn2, hw[wi + 6], hw[wi + 7], H, F, kFftKernel, mode, frames, 1.f);
-      put(hw[wi + 8], H, &L.g1); put(hw[wi + 9], H, &L.b1);
-      put(hw[wi + 10], H, &L.g2); put(hw[wi + 11], H, &L.b2);
+      arena.put(hw[wi + 8], H, &L.g1); arena.put(hw[wi + 9], H, &L.b1);
+      arena.put(hw[wi + 10], H, &L.g2); arena.put(hw[wi + 11], H, &L.b2);
       wi += 12;
     }
   };
   put_block(enc_, cfg_.encoder_num_layers, cfg_.encoder_ffn_channels, MATH_FP32_X6, false);
-  if (cfg_.positional_encoding) put(hw[wi++], (size_t)H * TTS_FORWARD_TTS_MAX_FRAMES, &pe_);
+  if (cfg_.positional_encoding) arena.put(hw[wi++], (size_t)H * TTS_FORWARD_TTS_MAX_FRAMES, &pe_);
   put_block(dec_, cfg_.decoder_num_layers, cfg_.decoder_ffn_channels, dec_mode_, true);
   put_conv(postnet_, hw[wi], hw[wi + 1], cfg_.out_channels, H, 1, dec_mode_, true, 1.f);
   wi += 2;
@@ -153,21 +137,13 @@ ForwardTts::ForwardTts(const TtsForwardTtsCfg& cfg, const float* const* hw, int 
     const TtsVitsDpCfg pc = predictor_cfg(H, cfg_.pitch_predictor_hidden_channels, cfg_.pitch_predictor_kernel_size);
     pp_ = std::make_unique<VitsDp>(pc, hw + wi, device_);
     wi += vits_dp_weight_shapes(pc).size();
-    put(hw[wi], (size_t)H * cfg_.pitch_embedding_kernel_size, &pitch_w_);
-    put(hw[wi + 1], H, &pitch_b_);
+    arena.put(hw[wi], (size_t)H * cfg_.pitch_embedding_kernel_size, &pitch_w_);
+    arena.put(hw[wi + 1], H, &pitch_b_);
     wi += 2;
   }
-  if (cfg_.num_speakers > 0) put(hw[wi++], (size_t)cfg_.num_speakers * H, &emb_g_);
+  if (cfg_.num_speakers > 0) arena.put(hw[wi++], (size_t)cfg_.num_speakers * H, &emb_g_);
   TTS_REQUIRE(wi == shapes.size(), 2, "internal: ForwardTTS weight count mismatch");
-  if (hipMalloc(&arena_, host.size() * sizeof(float)) != hipSuccess) throw Error(4, "hipMalloc(weights) failed");
-  TTS_HIP_CHECK(hipMemcpy(arena_, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
-  for (auto& p : fix) *p.second = arena_ + p.first;
-}
-
-ForwardTts::~ForwardTts() {
-  DeviceGuard g(device_);
-  if (arena_) (void)hipFree(arena_);
-  if (ws_) (void)hipFree(ws_);
+  arena.upload(device_, arena_);
 }
 
 // X0, X1 (layer state), A (attention output) [H]; Wd [max(3H, ffn)] (qkv / FFN hidden)
@@ -175,10 +151,7 @@ void ForwardTts::reserve(int B, int T) {
   const size_t H = cfg_.hidden_channels;
   const size_t big = std::max({3 * H, (size_t)cfg_.encoder_ffn_channels, (size_t)cfg_.decoder_ffn_channels});
   const size_t need = ((size_t)B * T * (3 * H + big) + 4 * 64) * sizeof(float);
-  if (need <= ws_bytes_) return;
-  if (ws_) { TTS_HIP_CHECK(hipFree(ws_)); ws_ = nullptr; ws_bytes_ = 0; }
-  if (hipMalloc(&ws_, need) != hipSuccess) throw Error(4, "hipMalloc(workspace) failed");
-  ws_bytes_ = need;
+  ws_.grow(device_, need, "workspace");
 }
 
 float* ForwardTts::run_layers(const std::vector<Layer>& layers, int mode, int heads, const int64_t* key_len, int B,
@@ -187,7 +160,7 @@ float* ForwardTts::run_layers(const std::vector<Layer>& layers, int mode, int he
   const size_t plane = (size_t)B * T;
   const double P = (double)plane;
   auto al = [](size_t n) { return (n + 63) & ~size_t(63); };
-  float* X0 = ws_;
+  float* X0 = ws_.as<>();
   float* X1 = X0 + al(plane * H);
   float* A = X1 + al(plane * H);
   float* Wd = A + al(plane * H);
@@ -228,7 +201,7 @@ void ForwardTts::block(bool decoder, const float* x, const int64_t* key_len, int
   DeviceGuard dg(device_);
   reserve(B, T);
   const size_t n = (size_t)B * T * cfg_.hidden_channels * sizeof(float);
-  TTS_HIP_CHECK(hipMemcpyAsync(ws_, x, n, hipMemcpyDeviceToDevice, s));
+  TTS_HIP_CHECK(hipMemcpyAsync(ws_.as<>(), x, n, hipMemcpyDeviceToDevice, s));
   const float* r = decoder ? run_layers(dec_, dec_mode_, cfg_.decoder_num_heads, key_len, B, T, s, prof, "dec")
                            : run_layers(enc_, MATH_FP32_X6, cfg_.encoder_num_heads, key_len, B, T, s, prof, "enc");
   TTS_HIP_CHECK(hipMemcpyAsync(y, r, n, hipMemcpyDeviceToDevice, s));
@@ -247,7 +220,7 @@ void ForwardTts::encode(const int64_t* tok, const int64_t* x_len, const int64_t*
   const int H = cfg_.hidden_channels;
   const double P = (double)B * T;
   run(prof, s, "enc_embed", 0.0, 4.0 * P * H + 16.0 * P,
-      [&] { launch_ftts_embed(tok, x_len, emb_, ws_, x_mask, B, H, T, cfg_.num_chars, s); });
+      [&] { launch_ftts_embed(tok, x_len, emb_, ws_.as<>(), x_mask, B, H, T, cfg_.num_chars, s); });
   const float* x = run_layers(enc_, MATH_FP32_X6, cfg_.encoder_num_heads, x_len, B, T, s, prof, "enc");
   run(prof, s, "enc_mask_speaker", 0.0, 8.0 * P * H, [&] {
     launch_ftts_mask_add(x, x_mask, cfg_.num_speakers > 0 ? emb_g_ : nullptr, spk, o_en, B, H, T, cfg_.num_speakers, s);
@@ -277,11 +250,11 @@ void ForwardTts::decode(const float* o_en, const float* dur, const float* x_mask
   // o_en_ex = attn^T o_en: every token column repeated dur times, zero past y_len
   ExpandArgs e{};
   e.w_ceil = dur; e.x_mask = x_mask; e.y_len = y_len; e.o_mean = o_en;
-  e.C = H; e.T_x = T; e.T_y = T_de; e.z = ws_; e.y_mask = y_mask; e.attn = attn;
+  e.C = H; e.T_x = T; e.T_y = T_de; e.z = ws_.as<>(); e.y_mask = y_mask; e.attn = attn;
   run(prof, s, "expand", 0.0, 4.0 * P * (2 * H + (attn ? T : 0)), [&] { launch_expand(e, B, s); });
   if (cfg_.positional_encoding)
     run(prof, s, "pos_encoding", 0.0, 12.0 * P * H, [&] {
-      launch_ftts_posenc(ws_, pe_, y_mask, B, H, T_de, TTS_FORWARD_TTS_MAX_FRAMES, sqrtf((float)H), s);
+      launch_ftts_posenc(ws_.as<>(), pe_, y_mask, B, H, T_de, TTS_FORWARD_TTS_MAX_FRAMES, sqrtf((float)H), s);
     });
   const float* x = run_layers(dec_, dec_mode_, cfg_.decoder_num_heads, mask_keys ? y_len : nullptr, B, T_de, s, prof,
                               "dec");

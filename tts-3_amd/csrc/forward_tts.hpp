@@ -34,9 +34,6 @@ std::vector<int64_t> forward_tts_weight_shapes(const TtsForwardTtsCfg& c);
 class ForwardTts {
  public:
   ForwardTts(const TtsForwardTtsCfg& cfg, const float* const* host_weights, int device);
-  ~ForwardTts();
-  ForwardTts(const ForwardTts&) = delete;
-  ForwardTts& operator=(const ForwardTts&) = delete;
 
   // Everything before the host read of y_len (text side, always fp32x6):
   //   o_en [B][H][T] = encoder(emb(tok)) * x_mask + emb_g[spk] (+ pitch_emb(pitch) with use_pitch)
@@ -54,11 +51,7 @@ class ForwardTts {
   int device() const { return device_; }
 
  private:
-  struct Conv {
-    int Cin = 0, Cout = 0, K = 1, tile = 0, n_chunks = 0;
-    float* w = nullptr;
-    float* b = nullptr;
-  };
+  using Conv = PackedConv;
   struct Layer {
     Conv qkv, o, ffn1, ffn2;  // o holds 2 out_proj: norm1 is LN(x + 2 a)
     float *g1 = nullptr, *b1 = nullptr, *g2 = nullptr, *b2 = nullptr;
@@ -78,9 +71,7 @@ class ForwardTts {
   std::unique_ptr<VitsDp> dp_, pp_;
   float *pitch_w_ = nullptr, *pitch_b_ = nullptr;
   float* emb_g_ = nullptr;
-  float* arena_ = nullptr;
-  float* ws_ = nullptr;
-  size_t ws_bytes_ = 0;
+  DeviceBuffer arena_, ws_;
 };
 
 }  // namespace tts

@@ -99,6 +99,21 @@ void gate_permute_rows(const float* w, const float* b, int H, int Cin, int K, st
   }
 }
 
+void put_flow_conv(HostArena& arena, PackedConv& cv, int mode, const float* w, const float* b, int Cin, int Cout, int K,
+                   int dil, bool gate) {
+  cv.Cin = Cin; cv.Cout = Cout; cv.K = K; cv.dil = dil;
+  cv.tile = flow_conv_tile(mode, Cout, K, Cin, dil);
+  cv.gated = gate && flow_gate_fused(mode, Cout / 2, K, dil);
+  std::vector<float> wperm, bperm;
+  if (cv.gated) {
+    gate_permute_rows(w, b, Cout / 2, Cin, K, wperm, bperm);
+    w = wperm.data();
+    b = bperm.data();
+    cv.tile = kSplitGateTile;
+  }
+  arena.put_conv(cv, mode, conv_tile(mode, cv.tile), w, b);
+}
+
 std::vector<int64_t> glow_weight_shapes(const TtsGlowDecoderCfg& c) {
   std::vector<int64_t> n;
   const int C2 = c.in_channels * c.num_squeeze;
@@ -173,49 +188,16 @@ GlowDecoder::GlowDecoder(const TtsGlowDecoderCfg& cfg, const float* const* hw, i
   const int S = cfg_.num_splits;
   const int L = cfg_.num_coupling_layers;
 
-  std::vector<float> host;
-  auto align = [](size_t n) { return (n + 63) & ~size_t(63); };
-  struct Pending { size_t off; float** dst; };
-  std::vector<std::pair<size_t, float**>> fix;  // (offset, pointer to patch)
-  auto put = [&](const float* src, size_t n, float** dst) {
-    const size_t off = host.size();
-    host.resize(off + align(n), 0.f);
-    std::memcpy(host.data() + off, src, n * sizeof(float));
-    fix.push_back({off, dst});
-  };
-  std::vector<float> wperm, bperm;
-  auto put_conv = [&](Conv& cv, const float* w, const float* b, int Cin, int Cout, int K, int dil,
-                      bool gate = false) {
-    cv.Cin = Cin; cv.Cout = Cout; cv.K = K; cv.dil = dil;
-    const int mode = cfg_.math_mode;
-    cv.tile = flow_conv_tile(mode, Cout, K, Cin, dil);
-    cv.gated = gate && flow_gate_fused(mode, Cout / 2, K, dil);
-    if (cv.gated) {
-      gate_permute_rows(w, b, Cout / 2, Cin, K, wperm, bperm);
-      w = wperm.data();
-      b = bperm.data();
-      cv.tile = kSplitGateTile;
-    }
-    const ConvTile t = conv_tile(mode, cv.tile);
-    cv.n_chunks = ceil_div(Cin, t.CK);
-    const size_t n = packed_conv_numel(mode, Cout, Cin, K, t);
-    const size_t off = host.size();
-    host.resize(off + align(n), 0.f);
-    cv.w_exp = pack_conv(mode, w, Cout, Cin, K, t, host.data() + off);
-    fix.push_back({off, &cv.w});
-    const size_t nb = (size_t)ceil_div(Cout, t.BM) * t.BM;
-    const size_t offb = host.size();
-    host.resize(offb + align(nb), 0.f);
-    std::memcpy(host.data() + offb, b, Cout * sizeof(float));
-    fix.push_back({offb, &cv.b});
-  };
+  HostArena arena;
+  auto put_conv = [&](PackedConv& cv, const float* w, const float* b, int Cin, int Cout, int K, int dil,
+                      bool gate = false) { put_flow_conv(arena, cv, cfg_.math_mode, w, b, Cin, Cout, K, dil, gate); };
 
   flows_.resize(cfg_.num_flow_blocks);
   size_t wi = 0;
   for (int f = 0; f < cfg_.num_flow_blocks; ++f) {
     Flow& F = flows_[f];
-    put(hw[wi], C2, &F.logs); put(hw[wi + 1], C2, &F.bias); put(hw[wi + 2], (size_t)S * S, &F.winv);
-    put(hw[wi + 3], (size_t)S * S, &F.w);
+    arena.put(hw[wi], C2, &F.logs); arena.put(hw[wi + 1], C2, &F.bias); arena.put(hw[wi + 2], (size_t)S * S, &F.winv);
+    arena.put(hw[wi + 3], (size_t)S * S, &F.w);
     {  // forward logdet per unmasked frame: torch.sum(logs) (normalization.py:100) and
        // torch.logdet(weight) * (C2 / S) (glow.py:128), here in fp64 from the fp32 parameters
       double sl = 0.0;
@@ -225,8 +207,8 @@ GlowDecoder::GlowDecoder(const TtsGlowDecoderCfg& cfg, const float* const* hw, i
     wi += 4;
     put_conv(F.start, hw[wi], hw[wi + 1], C2 / 2, H, 1, 1); wi += 2;
     if (cfg_.c_in_channels > 0) {  // cond_layer stays fp32 [2HL][c_in] (launch_cond_vec)
-      put(hw[wi], (size_t)2 * H * L * cfg_.c_in_channels, &F.cond_w);
-      put(hw[wi + 1], (size_t)2 * H * L, &F.cond_b);
+      arena.put(hw[wi], (size_t)2 * H * L * cfg_.c_in_channels, &F.cond_w);
+      arena.put(hw[wi + 1], (size_t)2 * H * L, &F.cond_b);
       wi += 2;
     }
     F.in_layers.resize(L); F.res_skip.resize(L);
@@ -239,15 +221,7 @@ GlowDecoder::GlowDecoder(const TtsGlowDecoderCfg& cfg, const float* const* hw, i
     }
     put_conv(F.end, hw[wi], hw[wi + 1], H, C2, 1, 1); wi += 2;
   }
-  if (hipMalloc(&arena_, host.size() * sizeof(float)) != hipSuccess) throw Error(4, "hipMalloc(weights) failed");
-  TTS_HIP_CHECK(hipMemcpy(arena_, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
-  for (auto& p : fix) *p.second = arena_ + p.first;
-}
-
-GlowDecoder::~GlowDecoder() {
-  DeviceGuard g(device_);
-  if (arena_) (void)hipFree(arena_);
-  if (ws_) (void)hipFree(ws_);
+  arena.upload(device_, arena_);
 }
 
 // f16x3 statistics: per flow (in execution order) 2L + 2 groups of [B][64] slots: the start conv's
@@ -268,10 +242,7 @@ void GlowDecoder::reserve(int B, int Th) {
   const size_t ldp = (size_t)cfg_.num_flow_blocks * B * kGlowLogdetParts * 2 + 64;
   const size_t need = plane * (2 * C2 + 7 * H + 1) * sizeof(float) + 64 * 10 * sizeof(float) +
                       (cond + amax_floats(B) + ldp) * sizeof(float);
-  if (need <= ws_bytes_) return;
-  if (ws_) { TTS_HIP_CHECK(hipFree(ws_)); ws_ = nullptr; ws_bytes_ = 0; }
-  if (hipMalloc(&ws_, need) != hipSuccess) throw Error(4, "hipMalloc(workspace) failed");
-  ws_bytes_ = need;
+  ws_.grow(device_, need, "workspace");
 }
 
 void GlowDecoder::reverse(const float* x, const float* mask, const float* g, int B, int C, int T, float* y,
@@ -301,7 +272,7 @@ void GlowDecoder::run_flows(bool rev, const float* x, const float* mask, const f
   const int NF = cfg_.num_flow_blocks;
   const size_t plane = (size_t)B * Th;
   auto al = [](size_t n) { return (n + 63) & ~size_t(63); };
-  float* p = ws_;
+  float* p = ws_.as<>();
   float* xs = p; p += al(plane * C2);
   float* hb = p; p += al(plane * H);
   float* xin = p; p += al(plane * 2 * H);

@@ -53,6 +53,11 @@ bool flow_amax_prepass();
 void gate_permute_rows(const float* w, const float* b, int H, int Cin, int K, std::vector<float>& wp,
                        std::vector<float>& bp);
 
+// One conv of a Glow / VITS flow into the arena: flow_conv_tile, or, for a gated in_layer, the rows
+// in gate_row_order on kSplitGateTile
+void put_flow_conv(HostArena& arena, PackedConv& cv, int mode, const float* w, const float* b, int Cin, int Cout, int K,
+                   int dil, bool gate = false);
+
 void launch_glow_gate(const float* xin, float* acts, int B, int H, int Th, hipStream_t s,
                       unsigned* amax = nullptr);
 void launch_glow_wn_update(float* h, float* skip, const float* rs, const float* mask, int B, int H,
@@ -156,9 +161,6 @@ void launch_channel_flip(const float* x, float* y, int B, int C, int T, hipStrea
 class GlowDecoder {
  public:
   GlowDecoder(const TtsGlowDecoderCfg& cfg, const float* const* host_weights, int device);
-  ~GlowDecoder();
-  GlowDecoder(const GlowDecoder&) = delete;
-  GlowDecoder& operator=(const GlowDecoder&) = delete;
   // g: [B][c_in_channels] speaker vector (the reference's g [B][c_in][1]), NULL when c_in_channels == 0
   void reverse(const float* x, const float* mask, const float* g, int B, int C, int T, float* y, hipStream_t s,
                Profiler* prof = nullptr);
@@ -168,12 +170,7 @@ class GlowDecoder {
   int device() const { return device_; }
 
  private:
-  struct Conv {
-    int Cin = 0, Cout = 0, K = 1, dil = 1, tile = 0, n_chunks = 0, w_exp = 0;
-    bool gated = false;  // in_layer with the WN gate fused (kSplitGateTile)
-    float* w = nullptr;
-    float* b = nullptr;
-  };
+  using Conv = PackedConv;
   struct Flow {
     float* logs = nullptr;
     float* bias = nullptr;
@@ -193,9 +190,7 @@ class GlowDecoder {
   TtsGlowDecoderCfg cfg_;
   int device_;
   std::vector<Flow> flows_;
-  float* arena_ = nullptr;
-  float* ws_ = nullptr;
-  size_t ws_bytes_ = 0;
+  DeviceBuffer arena_, ws_;
   bool amax_prepass_ = false;
   bool wn_fused_ = false;  // res_skip conv + WN update in one launch (flow_wn_fused)
   bool wn_layer_ = false;  // every WN layer in one launch (glow_wn_layer_kernel, flow_wn_layer)

@@ -136,16 +136,7 @@ GlowEncoder::GlowEncoder(const TtsGlowEncoderCfg& cfg, const float* const* hw, i
   const int D = cfg_.hidden_channels_dp;
   const int mode = cfg_.math_mode;
 
-  std::vector<float> host;
-  std::vector<std::pair<size_t, float**>> fix;
-  auto align = [](size_t n) { return (n + 63) & ~size_t(63); };
-  auto put = [&](const float* src, size_t n, float** dst) {
-    const size_t off = host.size();
-    host.resize(off + align(n), 0.f);
-    std::memcpy(host.data() + off, src, n * sizeof(float));
-    fix.push_back({off, dst});
-  };
-  // conv from one or more row blocks of torch weights [rows][Cin][K] stacked along Cout
+  HostArena arena;
   // conv from one or more row blocks of torch weights [rows][Cin][k] stacked along Cout; kc > k
   // appends zero taps (an even reference kernel on the odd-kernel conv); bn (weight, bias, mean,
   // var) folds a following BatchNorm into the weights and bias
@@ -158,8 +149,6 @@ GlowEncoder::GlowEncoder(const TtsGlowEncoderCfg& cfg, const float* const* hw, i
     // text batches are short (a 16 x 128-token batch is 2,048 columns): the split modes take the
     // 32x128 tile (4 waves side by side) so a conv launches Cout/32 x B workgroups, not Cout/128 x B
     cv.tile = is_split_mode(mode) ? 16 : conv_tile_for(mode, Cout, kc, Cin, dil, false);
-    const ConvTile t = conv_tile(mode, cv.tile);
-    cv.n_chunks = ceil_div(Cin, t.CK);
     std::vector<float> w((size_t)Cout * Cin * kc, 0.f), b(Cout);
     for (size_t p = 0; p < parts.size(); ++p) {
       for (int r = 0; r < rows_each; ++r)
@@ -175,21 +164,12 @@ GlowEncoder::GlowEncoder(const TtsGlowEncoderCfg& cfg, const float* const* hw, i
         b[co] = (float)(((double)b[co] - bn[2][co]) * sc + bn[1][co]);
       }
     }
-    const size_t n = packed_conv_numel(mode, Cout, Cin, kc, t);
-    const size_t off = host.size();
-    host.resize(off + align(n), 0.f);
-    const int w_exp = pack_conv(mode, w.data(), Cout, Cin, kc, t, host.data() + off);
+    const int w_exp = arena.put_conv(cv, mode, conv_tile(mode, cv.tile), w.data(), b.data());
     TTS_REQUIRE(w_exp == 0, 3, "Glow encoder: scaled weight packing is not supported");
-    fix.push_back({off, &cv.w});
-    const size_t nb = (size_t)ceil_div(Cout, t.BM) * t.BM;
-    const size_t offb = host.size();
-    host.resize(offb + align(nb), 0.f);
-    std::memcpy(host.data() + offb, b.data(), Cout * sizeof(float));
-    fix.push_back({offb, &cv.b});
   };
   auto put_norm = [&](Norm& n, const float* gm, const float* bt, int C) {
-    put(gm, C, &n.gamma);
-    put(bt, C, &n.beta);
+    arena.put(gm, C, &n.gamma);
+    arena.put(bt, C, &n.beta);
   };
 
   // BatchNorm (weight, bias, running_mean, running_var) -> device scale / shift
@@ -200,13 +180,13 @@ GlowEncoder::GlowEncoder(const TtsGlowEncoderCfg& cfg, const float* const* hw, i
       sc[c] = (float)s;
       sh[c] = (float)((double)bn[1][c] - (double)bn[2][c] * s);
     }
-    put(sc.data(), C, &af.scale);
-    put(sh.data(), C, &af.shift);
+    arena.put(sc.data(), C, &af.scale);
+    arena.put(sh.data(), C, &af.shift);
   };
   const int et = cfg_.encoder_type;
 
   size_t wi = 0;
-  put(hw[wi++], (size_t)cfg_.num_chars * emb_ch_, &emb_);
+  arena.put(hw[wi++], (size_t)cfg_.num_chars * emb_ch_, &emb_);
   if (cfg_.use_prenet && (et == TTS_ENC_REL_POS_TRANSFORMER || et == TTS_ENC_TIME_DEPTH_SEPARABLE)) {
     for (int l = 0; l < 3; ++l) {
       put_conv(pre_conv_[l], {{hw[wi], hw[wi + 1]}}, H, H, 5);
@@ -254,8 +234,8 @@ GlowEncoder::GlowEncoder(const TtsGlowEncoderCfg& cfg, const float* const* hw, i
         for (int j = 0; j < k; ++j) dw[(size_t)c * k + j] = (float)(hw[wi][(size_t)c * k + j] * sc);
         db[c] = (float)(((double)hw[wi + 1][c] - hw[wi + 4][c]) * sc + hw[wi + 3][c]);
       }
-      put(dw.data(), dw.size(), &L.dw_w);
-      put(db.data(), db.size(), &L.dw_b);
+      arena.put(dw.data(), dw.size(), &L.dw_w);
+      arena.put(db.data(), db.size(), &L.dw_b);
       wi += 6;
       put_conv(L.time_conv2, {{hw[wi], hw[wi + 1]}}, H, H, 1, 1, 0, 0, hw + wi + 2);
       wi += 6;
@@ -269,8 +249,8 @@ GlowEncoder::GlowEncoder(const TtsGlowEncoderCfg& cfg, const float* const* hw, i
     wi += 8;
     if (cfg_.rel_attn_window_size > 0) {
       const size_t R = 2 * cfg_.rel_attn_window_size + 1;
-      put(hw[wi], R * heads_dk(cfg_), &L.ek);
-      put(hw[wi + 1], R * heads_dk(cfg_), &L.ev);
+      arena.put(hw[wi], R * heads_dk(cfg_), &L.ek);
+      arena.put(hw[wi + 1], R * heads_dk(cfg_), &L.ev);
       wi += 2;
     }
     put_norm(L.n1, hw[wi], hw[wi + 1], H);
@@ -295,15 +275,7 @@ GlowEncoder::GlowEncoder(const TtsGlowEncoderCfg& cfg, const float* const* hw, i
   }
   TTS_REQUIRE(wi == shapes.size(), 2, "internal: Glow encoder weight count mismatch");
 
-  if (hipMalloc(&arena_, host.size() * sizeof(float)) != hipSuccess) throw Error(4, "hipMalloc(weights) failed");
-  TTS_HIP_CHECK(hipMemcpy(arena_, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
-  for (auto& p : fix) *p.second = arena_ + p.first;
-}
-
-GlowEncoder::~GlowEncoder() {
-  DeviceGuard g(device_);
-  if (arena_) (void)hipFree(arena_);
-  if (ws_) (void)hipFree(ws_);
+  arena.upload(device_, arena_);
 }
 
 void GlowEncoder::reserve(int B, int T) {
@@ -312,10 +284,7 @@ void GlowEncoder::reserve(int B, int T) {
   const size_t big = std::max({(size_t)3 * H, (size_t)F, (size_t)D});
   const size_t dpin = cfg_.c_in_channels > 0 ? plane * (H + cfg_.c_in_channels) + 64 : 0;  // cat(x, g) * mask
   const size_t need = (plane * (3 * (size_t)H + big + std::max((size_t)H, (size_t)D)) + dpin) * sizeof(float) + 4096;
-  if (need <= ws_bytes_) return;
-  if (ws_) { TTS_HIP_CHECK(hipFree(ws_)); ws_ = nullptr; ws_bytes_ = 0; }
-  if (hipMalloc(&ws_, need) != hipSuccess) throw Error(4, "hipMalloc(workspace) failed");
-  ws_bytes_ = need;
+  ws_.grow(device_, need, "workspace");
 }
 
 void GlowEncoder::forward(const int64_t* tok, const int64_t* len, const float* g, int B, int T, float* x_m,
@@ -336,7 +305,7 @@ void GlowEncoder::forward(const int64_t* tok, const int64_t* len, const float* g
   const size_t plane = (size_t)B * T;
   const double P = (double)plane;
   auto al = [](size_t n) { return (n + 63) & ~size_t(63); };
-  float* p = ws_;
+  float* p = ws_.as<>();
   float* X0 = p; p += al(plane * H);   // layer state ping
   float* X1 = p; p += al(plane * H);   // layer state pong
   float* A = p; p += al(plane * H);    // attention output

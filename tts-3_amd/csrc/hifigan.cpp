@@ -7,7 +7,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
-#include <cstring>
 #include <vector>
 
 namespace tts {
@@ -99,7 +98,7 @@ Hifigan::Hifigan(const TtsHifiganCfg& cfg, const float* const* hw, int device)
   for (size_t i = 0; i < shapes.size(); ++i)
     TTS_REQUIRE(hw[i] != nullptr, 1, "weight pointer " + std::to_string(i) + " is NULL");
 
-  // 1) describe layers, 2) size the arena, 3) pack on host, 4) one upload.
+  // 1) describe layers, 2) pack on host in arena order, 3) one upload.
   const int C0 = cfg_.upsample_initial_channel;
   const int mode = cfg_.math_mode;
   // TTS_MI355X_NO_PAIR_FUSION=1 keeps every resblock conv a separate launch (the tests' reference arm)
@@ -128,10 +127,6 @@ Hifigan::Hifigan(const TtsHifiganCfg& cfg, const float* const* hw, int device)
       // a bf16 128-channel pair (resblock_pair128): the direct packing with 16-channel chunks
       // (tile 7: 128 x 128, one 16-channel group per chunk) instead of the Winograd packing
       L.tile = 7;
-      const ConvTile t = conv_tile(lmode, L.tile);
-      L.n_chunks = ceil_div(Cin, t.CK);
-      L.w_numel = packed_conv_numel(lmode, Cout, Cin, K, t);
-      L.b_numel = (int64_t)ceil_div(Cout, t.BM) * t.BM;
       L.name = std::string(fam) + "_k" + std::to_string(K) + "_c" + std::to_string(Cout);
       return L;
     }
@@ -151,10 +146,6 @@ Hifigan::Hifigan(const TtsHifiganCfg& cfg, const float* const* hw, int device)
       L.tile = kSplitWinoTile;
       fam = "mrf_wino";
     }
-    const ConvTile t = conv_tile(lmode, L.tile);
-    L.n_chunks = ceil_div(Cin, t.CK);
-    L.w_numel = packed_conv_numel(lmode, Cout, Cin, K, t);
-    L.b_numel = (int64_t)ceil_div(Cout, t.BM) * t.BM;
     L.name = std::string(fam) + "_k" + std::to_string(K) + "_c" + std::to_string(Cout);
     return L;
   };
@@ -165,20 +156,8 @@ Hifigan::Hifigan(const TtsHifiganCfg& cfg, const float* const* hw, int device)
     ConvTLayer L;
     L.Cin = C0 >> i; L.Cout = C0 >> (i + 1); L.U = cfg_.upsample_factors[i];
     L.mode = mode;
-    if (is_split_mode(mode)) {
-      // split modes: the K=2 polyphase conv form (Conv1dArgs::ups), U*Cout rows
-      L.tile = conv_tile_for(mode, L.U * L.Cout, 2, L.Cin, 1, false);
-      const ConvTile t = conv_tile(mode, L.tile);
-      L.n_chunks = ceil_div(L.Cin, t.CK);
-      L.w_numel = packed_conv_numel(mode, L.U * L.Cout, L.Cin, 2, t);
-      L.b_numel = (int64_t)ceil_div(L.U * L.Cout, t.BM) * t.BM;
-    } else {
-      L.tile = convT_tile_for(L.Cout, L.U);
-      const ConvTile t = convT_tile(L.tile, L.U);
-      L.n_chunks = ceil_div(L.Cin, t.CK);
-      L.w_numel = packed_convT_numel(L.Cin, L.Cout, L.U, t);
-      L.b_numel = (int64_t)ceil_div(L.Cout, t.BM) * t.BM;
-    }
+    // split modes: the K=2 polyphase conv form (Conv1dArgs::ups), U*Cout rows
+    L.tile = is_split_mode(mode) ? conv_tile_for(mode, L.U * L.Cout, 2, L.Cin, 1, false) : convT_tile_for(L.Cout, L.U);
     L.name = "ups_u" + std::to_string(L.U) + "_c" + std::to_string(L.Cout);
     ups_.push_back(L);
   }
@@ -254,89 +233,55 @@ Hifigan::Hifigan(const TtsHifiganCfg& cfg, const float* const* hw, int device)
       res_.push_back(rb);
     }
   }
-  post_w_ = hw[wi]; wi += 1;
+  const float* post_w = hw[wi]; wi += 1;
   post_bias_ = cfg_.conv_post_bias ? hw[wi][0] : 0.f;
   if (cfg_.conv_post_bias) wi += 1;
-  const float* cond_w = nullptr; const float* cond_b = nullptr;
-  if (cfg_.cond_channels > 0) { cond_w = hw[wi]; cond_b = hw[wi + 1]; wi += 2; }
-  std::vector<std::pair<const float*, const float*>> upcond;  // conds.i (XTTS)
-  if (cfg_.cond_in_each_up_layer)
-    for (int i = 0; i < cfg_.num_upsamples; ++i) { upcond.push_back({hw[wi], hw[wi + 1]}); wi += 2; }
 
-  // arena layout
+  // arena order: conv_pre and the resblock convs (execution order c1_0, c2_0, c1_1, ..., as src),
+  // upsamplers, conv_post, cond_layer, conds.i (XTTS)
+  HostArena arena;
   std::vector<ConvLayer*> convs;
   convs.push_back(&pre_);
   for (auto& rb : res_) for (auto& c : rb.convs) convs.push_back(&c);
-  int64_t total = 0;
-  auto align = [](int64_t n) { return (n + 63) & ~int64_t(63); };
-  for (auto* c : convs) total += align(c->w_numel) + align(c->b_numel);
-  for (auto& u : ups_) total += align(u.w_numel) + align(u.b_numel);
-  const int Cl = C0 >> cfg_.num_upsamples;
-  total += align((int64_t)Cl * 7);
-  if (cfg_.cond_channels > 0) total += align((int64_t)C0 * cfg_.cond_channels) + align(C0);
-  for (size_t i = 0; i < upcond.size(); ++i)
-    total += align((int64_t)(C0 >> (i + 1)) * cfg_.cond_channels) + align(C0 >> (i + 1));
-
-  std::vector<float> host(total, 0.f);
-  int64_t off = 0;
-  std::vector<int64_t> offs;
-  // conv1d layers: src[] is in the same order as convs[] (pre, then resblock convs)
-  // resblock convs were pushed in execution order (c1_0, c2_0, c1_1, ...), matching src.
-  {
-    // src[0] is conv_pre; src[1..] resblocks
-    size_t si = 0;
-    for (auto* c : convs) {
-      const ConvTile t = conv_tile(c->mode, c->tile);
-      c->w_exp = pack_conv(c->mode, src[si].first, c->Cout, c->Cin, c->K, t, host.data() + off);
-      offs.push_back(off); off += align(c->w_numel);
-      std::memcpy(host.data() + off, src[si].second, sizeof(float) * c->Cout);
-      offs.push_back(off); off += align(c->b_numel);
-      ++si;
-    }
+  for (size_t i = 0; i < convs.size(); ++i) {
+    ConvLayer& c = *convs[i];
+    arena.put_conv(c, c.mode, conv_tile(c.mode, c.tile), src[i].first, src[i].second);
   }
   for (size_t i = 0; i < ups_.size(); ++i) {
     auto& u = ups_[i];
     if (is_split_mode(u.mode)) {
       const ConvTile t = conv_tile(u.mode, u.tile);
-      u.w_exp = pack_convT_split(u.mode, usrc[i].first, u.Cin, u.Cout, u.U, t, host.data() + off);
-      offs.push_back(off); off += align(u.w_numel);
+      u.n_chunks = ceil_div(u.Cin, t.CK);
+      const size_t o = arena.alloc(packed_conv_numel(u.mode, u.U * u.Cout, u.Cin, 2, t), &u.w);
+      u.w_exp = pack_convT_split(u.mode, usrc[i].first, u.Cin, u.Cout, u.U, t, arena.at(o));
+      std::vector<float> bias((size_t)u.U * u.Cout);  // the conv's bias repeated per phase
       for (int co = 0; co < u.Cout; ++co)
-        for (int ph = 0; ph < u.U; ++ph) host[off + (int64_t)co * u.U + ph] = usrc[i].second[co];
+        for (int ph = 0; ph < u.U; ++ph) bias[(size_t)co * u.U + ph] = usrc[i].second[co];
+      arena.put_bias(bias.data(), u.U * u.Cout, t, &u.b);
     } else {
       const ConvTile t = convT_tile(u.tile, u.U);
-      pack_convT(usrc[i].first, u.Cin, u.Cout, u.U, t, host.data() + off);
-      offs.push_back(off); off += align(u.w_numel);
-      std::memcpy(host.data() + off, usrc[i].second, sizeof(float) * u.Cout);
+      u.n_chunks = ceil_div(u.Cin, t.CK);
+      const size_t o = arena.alloc(packed_convT_numel(u.Cin, u.Cout, u.U, t), &u.w);
+      pack_convT(usrc[i].first, u.Cin, u.Cout, u.U, t, arena.at(o));
+      arena.put_bias(usrc[i].second, u.Cout, t, &u.b);
     }
-    offs.push_back(off); off += align(u.b_numel);
   }
-  std::memcpy(host.data() + off, post_w_, sizeof(float) * Cl * 7);
-  const int64_t post_off = off; off += align((int64_t)Cl * 7);
-  int64_t cond_w_off = -1, cond_b_off = -1;
+  arena.put(post_w, (size_t)(C0 >> cfg_.num_upsamples) * 7, &post_wd_);
   if (cfg_.cond_channels > 0) {
-    std::memcpy(host.data() + off, cond_w, sizeof(float) * C0 * cfg_.cond_channels);
-    cond_w_off = off; off += align((int64_t)C0 * cfg_.cond_channels);
-    std::memcpy(host.data() + off, cond_b, sizeof(float) * C0);
-    cond_b_off = off; off += align(C0);
+    arena.put(hw[wi], (size_t)C0 * cfg_.cond_channels, &cond_wd_);
+    arena.put(hw[wi + 1], C0, &cond_bd_);
+    wi += 2;
   }
-  std::vector<std::pair<int64_t, int64_t>> upcond_off;
-  for (size_t i = 0; i < upcond.size(); ++i) {
-    const int64_t ci = C0 >> (i + 1);
-    std::memcpy(host.data() + off, upcond[i].first, sizeof(float) * ci * cfg_.cond_channels);
-    const int64_t wo = off; off += align(ci * cfg_.cond_channels);
-    std::memcpy(host.data() + off, upcond[i].second, sizeof(float) * ci);
-    upcond_off.push_back({wo, off}); off += align(ci);
+  if (cfg_.cond_in_each_up_layer) {  // conds.i (XTTS)
+    up_cond_.resize(cfg_.num_upsamples);
+    for (int i = 0; i < cfg_.num_upsamples; ++i) {
+      const size_t ci = C0 >> (i + 1);
+      arena.put(hw[wi], ci * cfg_.cond_channels, &up_cond_[i].first);
+      arena.put(hw[wi + 1], ci, &up_cond_[i].second);
+      wi += 2;
+    }
   }
-
-  weights_bytes_ = (size_t)total * sizeof(float);
-  if (hipMalloc(&arena_, weights_bytes_) != hipSuccess) throw Error(4, "hipMalloc(weights) failed");
-  TTS_HIP_CHECK(hipMemcpy(arena_, host.data(), weights_bytes_, hipMemcpyHostToDevice));
-  size_t oi = 0;
-  for (auto* c : convs) { c->w = arena_ + offs[oi++]; c->b = arena_ + offs[oi++]; }
-  for (auto& u : ups_) { u.w = arena_ + offs[oi++]; u.b = arena_ + offs[oi++]; }
-  post_wd_ = arena_ + post_off;
-  if (cfg_.cond_channels > 0) { cond_wd_ = arena_ + cond_w_off; cond_bd_ = arena_ + cond_b_off; }
-  for (auto& o : upcond_off) up_cond_.push_back({arena_ + o.first, arena_ + o.second});
+  arena.upload(device_, arena_);
   hop_ = 1;
   for (int i = 0; i < cfg_.num_upsamples; ++i) hop_ *= cfg_.upsample_factors[i];
 }
@@ -351,9 +296,6 @@ Hifigan::~Hifigan() {
     if (ln.ev_done) (void)hipEventDestroy(ln.ev_done);
   }
   if (ev_start_) (void)hipEventDestroy(ev_start_);
-  if (arena_) (void)hipFree(arena_);
-  if (ws_) (void)hipFree(ws_);
-  if (win_) (void)hipFree(win_);
 }
 
 int64_t Hifigan::out_len(int T, int pad) const { return (int64_t)hop_ * (T + 2 * pad); }
@@ -498,11 +440,7 @@ int64_t Hifigan::workspace_bytes(int B, int T, int pad) const {
 
 void Hifigan::reserve_plain(int B, int64_t L, bool window) {
   const int64_t need = plain_workspace_bytes(B, L, window);
-  if ((size_t)need <= ws_bytes_) return;
-  DeviceGuard g(device_);
-  if (ws_) { TTS_HIP_CHECK(hipFree(ws_)); ws_ = nullptr; ws_bytes_ = 0; }
-  if (hipMalloc(&ws_, need) != hipSuccess) throw Error(4, "hipMalloc(workspace) failed");
-  ws_bytes_ = need;
+  ws_.grow(device_, (size_t)need, "workspace");
 }
 
 void Hifigan::reserve(int B, int T, int pad) {
@@ -513,12 +451,7 @@ void Hifigan::reserve(int B, int T, int pad) {
   }
   const int64_t W = std::min<int64_t>(L, window_payload() + 2 * window_halo());
   reserve_plain(B, W, true);
-  const int64_t need = window_buffer_bytes(B, W);
-  if ((size_t)need <= win_bytes_) return;
-  DeviceGuard g(device_);
-  if (win_) { TTS_HIP_CHECK(hipFree(win_)); win_ = nullptr; win_bytes_ = 0; }
-  if (hipMalloc(&win_, need) != hipSuccess) throw Error(4, "hipMalloc(window buffers) failed");
-  win_bytes_ = need;
+  win_.grow(device_, (size_t)window_buffer_bytes(B, W), "window buffers");
 }
 
 void Hifigan::forward(const float* mel, int B, int C, int T, int pad, const float* gvec, float* wav,
@@ -536,7 +469,7 @@ void Hifigan::forward(const float* mel, int B, int C, int T, int pad, const floa
     reserve_plain(B, L);
     // a profiled forward stays on one stream (its per-launch timings are serial)
     if (prof) {
-      forward_plain(mel, B, C, T, pad, gvec, wav, s, prof, ws_, nullptr);
+      forward_plain(mel, B, C, T, pad, gvec, wav, s, prof, ws_.as<>(), nullptr);
       return;
     }
     ensure_lanes();
@@ -544,13 +477,13 @@ void Hifigan::forward(const float* mel, int B, int C, int T, int pad, const floa
     // split batches run one stream per lane unless TTS_MI355X_MRF_STREAMS says otherwise
     for (Lane& ln : lanes_) ln.nbs = nl > 1 ? split_nbs() : nbs_;
     if (nl == 1) {
-      forward_plain(mel, B, C, T, pad, gvec, wav, s, nullptr, ws_, &lanes_[0]);
+      forward_plain(mel, B, C, T, pad, gvec, wav, s, nullptr, ws_.as<>(), &lanes_[0]);
       return;
     }
     // sub-batches on concurrent lanes: lane 0 on the caller's stream, lane i > 0 on its own stream
     // after everything enqueued on s so far; s waits for every lane at the end
     TTS_HIP_CHECK(hipEventRecord(ev_start_, s));
-    float* ws = ws_;
+    float* ws = ws_.as<>();
     int b0 = 0;
     for (int i = 0; i < nl; ++i) {
       const int Bi = lane_batch(B, i);
@@ -575,8 +508,8 @@ void Hifigan::forward(const float* mel, int B, int C, int T, int pad, const floa
   const int64_t P = window_payload();
   TTS_REQUIRE(P >= 1, 3, "window payload must be >= 1 frame");
   const int64_t Wmax = std::min<int64_t>(L, P + 2 * h);
-  float* melw = win_;
-  float* outw = win_ + (((int64_t)B * C * Wmax + 63) / 64) * 64;
+  float* melw = win_.as<>();
+  float* outw = melw + (((int64_t)B * C * Wmax + 63) / 64) * 64;
   for (int64_t s0 = 0; s0 < L; s0 += P) {
     const int64_t s1 = std::min(L, s0 + P);
     const int64_t w0 = std::max<int64_t>(0, s0 - h), w1 = std::min(L, s1 + h);
@@ -588,7 +521,7 @@ void Hifigan::forward(const float* mel, int B, int C, int T, int pad, const floa
       ensure_lanes();
       lanes_[0].nbs = nbs_;
     }
-    forward_plain(melw, B, C, W, 0, gvec, outw, s, prof, ws_, prof ? nullptr : &lanes_[0]);
+    forward_plain(melw, B, C, W, 0, gvec, outw, s, prof, ws_.as<>(), prof ? nullptr : &lanes_[0]);
     // the payload's samples: outw[b][hop*(s0-w0) ...) -> wav[b][hop*s0 ...)
     TTS_HIP_CHECK(hipMemcpy2DAsync(wav + hop_ * s0, sizeof(float) * hop_ * L, outw + hop_ * (s0 - w0),
                                    sizeof(float) * hop_ * W, sizeof(float) * hop_ * (s1 - s0), B,

@@ -5,23 +5,11 @@
 #include <string>
 #include <vector>
 
+#include "arena.hpp"
 #include "common.hpp"
 #include "tts_mi355x.h"
 
 namespace tts {
-
-// Restores the caller's current HIP device on scope exit (torch keeps its own notion).
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int dev) {
-    TTS_HIP_CHECK(hipGetDevice(&prev));
-    if (prev != dev) TTS_HIP_CHECK(hipSetDevice(dev));
-  }
-  ~DeviceGuard() {
-    int cur = -1;
-    if (hipGetDevice(&cur) == hipSuccess && cur != prev && prev >= 0) (void)hipSetDevice(prev);
-  }
-};
 
 // Per-launch hipEvent timing for *_profiled entry points.
 struct Profiler {
@@ -80,22 +68,13 @@ class Hifigan {
   int64_t window_payload() const;     // payload frames per window
 
  private:
-  struct ConvLayer {
-    int Cin = 0, Cout = 0, K = 0, dil = 1, pad = 0, tile = 0, n_chunks = 0;
-    int mode = 0;   // math mode of this layer (TTS_MATH_*)
-    int w_exp = 0;  // packed weights hold w * 2^-w_exp (fp16 hi/lo mode)
-    int64_t w_numel = 0, b_numel = 0;
-    float* w = nullptr;
-    float* b = nullptr;
+  struct ConvLayer : PackedConv {
+    int mode = 0;  // math mode of this layer (TTS_MATH_*)
     std::string name;
   };
-  struct ConvTLayer {
-    int Cin = 0, Cout = 0, U = 0, tile = 0, n_chunks = 0;
-    int mode = 0;   // split modes run the K=2 polyphase conv form (Conv1dArgs::ups)
-    int w_exp = 0;
-    int64_t w_numel = 0, b_numel = 0;
-    float* w = nullptr;
-    float* b = nullptr;
+  struct ConvTLayer : PackedConv {  // Cout: channels (the packed conv has U * Cout rows in the split modes)
+    int U = 0;
+    int mode = 0;  // split modes run the K=2 polyphase conv form (Conv1dArgs::ups)
     std::string name;
   };
   struct ResBlock {
@@ -153,18 +132,13 @@ class Hifigan {
   ConvLayer pre_;
   std::vector<ConvTLayer> ups_;
   std::vector<ResBlock> res_;
-  const float* post_w_ = nullptr;  // host pointer, only valid during construction
   float post_bias_ = 0.f;
   float* post_wd_ = nullptr;
   float* cond_wd_ = nullptr;
   float* cond_bd_ = nullptr;
   std::vector<std::pair<float*, float*>> up_cond_;  // conds.i (w [C_i][cond], b [C_i]), XTTS
-  float* arena_ = nullptr;
-  size_t weights_bytes_ = 0;
-  float* ws_ = nullptr;
-  size_t ws_bytes_ = 0;
-  float* win_ = nullptr;  // windowed forward: gathered mel window [B][C][W] + window output [B][hop*W]
-  size_t win_bytes_ = 0;
+  DeviceBuffer arena_, ws_;
+  DeviceBuffer win_;  // windowed forward: gathered mel window [B][C][W] + window output [B][hop*W]
 };
 
 }  // namespace tts

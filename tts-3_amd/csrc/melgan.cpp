@@ -4,7 +4,6 @@
 #include "melgan.hpp"
 
 #include <algorithm>
-#include <cstring>
 
 namespace tts {
 
@@ -106,45 +105,35 @@ Melgan::Melgan(const TtsMelganCfg& cfg, const float* const* hw, int device) : cf
   TTS_REQUIRE(device >= 0 && device < dev_count, 1, "melgan: bad device index");
 
   const int base = cfg.base_channels, n = cfg.num_ups, NB = cfg.num_res_blocks;
-  auto align = [](int64_t v) { return (v + 63) & ~int64_t(63); };
-  int64_t total = 0;
+  // arena order: first conv, upsamplers, residual blocks, tail, PQMF filters
+  HostArena arena;
   size_t wi = 0;
-  struct Src {
-    const float *w, *b;
-  };
   // first conv (pad 0 on the gathered input)
   pre_.Cin = cfg.in_channels; pre_.Cout = base; pre_.K = cfg.proj_kernel;
   pre_.tile = conv_tile_for(mode_, base, pre_.K, pre_.Cin, 1, false);
-  {
-    const ConvTile t = conv_tile(mode_, pre_.tile);
-    pre_.n_chunks = ceil_div(pre_.Cin, t.CK);
-    pre_.w_numel = packed_conv_numel(mode_, base, pre_.Cin, pre_.K, t);
-    pre_.b_numel = (int64_t)ceil_div(base, t.BM) * t.BM;
-  }
   pre_.name = "conv_pre_k" + std::to_string(pre_.K) + "_c" + std::to_string(base);
-  const Src pre_src{hw[wi], hw[wi + 1]};
+  (void)arena.put_conv(pre_, mode_, conv_tile(mode_, pre_.tile), hw[wi], hw[wi + 1]);
   wi += 2;
-  total += align(pre_.w_numel) + align(pre_.b_numel);
 
-  std::vector<Src> ups_src;
   struct BlockSrc {
     const float *w1, *b1, *w2, *b2, *ws, *bs;
   };
   std::vector<BlockSrc> blk_src;
+  ups_.resize(n);
   for (int i = 0; i < n; ++i) {
-    Conv u;
+    Conv& u = ups_[i];
     u.Cin = base >> i; u.Cout = base >> (i + 1); u.U = cfg.upsample_factors[i]; u.K = 2;
     u.tile = conv_tile_for(mode_, u.U * u.Cout, 2, u.Cin, 1, false);
     const ConvTile t = conv_tile(mode_, u.tile);
     u.n_chunks = ceil_div(u.Cin, t.CK);
-    u.w_numel = packed_conv_numel(mode_, u.U * u.Cout, u.Cin, 2, t);
-    u.b_numel = (int64_t)ceil_div(u.U * u.Cout, t.BM) * t.BM;
     u.name = "ups_u" + std::to_string(u.U) + "_c" + std::to_string(u.Cout);
-    ups_src.push_back({hw[wi], hw[wi + 1]});
+    const size_t o = arena.alloc(packed_conv_numel(mode_, u.U * u.Cout, u.Cin, 2, t), &u.w);
+    (void)pack_convT_split(mode_, hw[wi], u.Cin, u.Cout, u.U, t, arena.at(o));
+    std::vector<float> bias((size_t)u.U * u.Cout);  // the conv's bias repeated per phase
+    for (int co = 0; co < u.Cout; ++co)
+      for (int ph = 0; ph < u.U; ++ph) bias[(size_t)co * u.U + ph] = hw[wi + 1][co];
+    arena.put_bias(bias.data(), u.U * u.Cout, t, &u.b);
     wi += 2;
-    total += align(u.w_numel) + align(u.b_numel);
-    ups_.push_back(u);
-    const int C = u.Cout;
     std::vector<BlockSrc> bs(NB);
     for (int j = 0; j < NB; ++j) {
       bs[j].w1 = hw[wi]; bs[j].b1 = hw[wi + 1]; bs[j].w2 = hw[wi + 2]; bs[j].b2 = hw[wi + 3];
@@ -156,91 +145,30 @@ Melgan::Melgan(const TtsMelganCfg& cfg, const float* const* hw, int device) : cf
     }
     for (int j = 0; j < NB; ++j) {
       Block bl;
-      bl.C = C; bl.dil = ipow(cfg.res_kernel, j);
-      bl.a1_numel16 = packed_melgan_a1_numel16(mode_, C);
-      bl.a2_numel16 = packed_melgan_a2_numel16(mode_, C);
-      bl.name = "res_block_d" + std::to_string(bl.dil) + "_c" + std::to_string(C);
-      total += align(bl.a1_numel16 / 2) + align(bl.a2_numel16 / 2) + 2 * align(32 * melgan_mblocks(C));
+      bl.C = u.Cout; bl.dil = ipow(cfg.res_kernel, j);
+      bl.a1_numel16 = packed_melgan_a1_numel16(mode_, bl.C);
+      bl.a2_numel16 = packed_melgan_a2_numel16(mode_, bl.C);
+      bl.name = "res_block_d" + std::to_string(bl.dil) + "_c" + std::to_string(bl.C);
       blocks_.push_back(bl);
       blk_src.push_back(bs[j]);
     }
   }
-  const int Cl = base >> n;
-  const float* tail_w = hw[wi];
-  const float* tail_b = hw[wi + 1];
-  wi += 2;
-  const int64_t tail_w_numel = (int64_t)cfg.out_channels * Cl * cfg.proj_kernel;
-  total += align(tail_w_numel) + align(cfg.out_channels);
-  const float* g_src = cfg.pqmf_bands > 0 ? hw[wi++] : nullptr;
-  const int64_t g_numel = cfg.pqmf_bands > 0 ? (int64_t)cfg.pqmf_bands * (cfg.pqmf_taps + 1) : 0;
-  total += align(g_numel);
-
-  std::vector<float> host((size_t)total, 0.f);
-  int64_t off = 0;
-  auto take = [&](int64_t numel) {
-    const int64_t o = off;
-    off += align(numel);
-    return o;
-  };
-  std::vector<int64_t> offs;
-  {
-    const ConvTile t = conv_tile(mode_, pre_.tile);
-    int64_t o = take(pre_.w_numel);
-    (void)pack_conv(mode_, pre_src.w, pre_.Cout, pre_.Cin, pre_.K, t, host.data() + o);
-    offs.push_back(o);
-    o = take(pre_.b_numel);
-    std::memcpy(host.data() + o, pre_src.b, sizeof(float) * pre_.Cout);
-    offs.push_back(o);
-  }
-  for (size_t i = 0; i < ups_.size(); ++i) {
-    const Conv& u = ups_[i];
-    const ConvTile t = conv_tile(mode_, u.tile);
-    int64_t o = take(u.w_numel);
-    (void)pack_convT_split(mode_, ups_src[i].w, u.Cin, u.Cout, u.U, t, host.data() + o);
-    offs.push_back(o);
-    o = take(u.b_numel);
-    for (int co = 0; co < u.Cout; ++co)
-      for (int ph = 0; ph < u.U; ++ph) host[o + (int64_t)co * u.U + ph] = ups_src[i].b[co];
-    offs.push_back(o);
-  }
   for (size_t i = 0; i < blocks_.size(); ++i) {
-    const Block& bl = blocks_[i];
+    Block& bl = blocks_[i];
     const BlockSrc& s = blk_src[i];
-    const int64_t o1 = take(bl.a1_numel16 / 2), o2 = take(bl.a2_numel16 / 2);
-    const int64_t ob1 = take(32 * melgan_mblocks(bl.C)), ob2 = take(32 * melgan_mblocks(bl.C));
-    pack_melgan_block(mode_, s.w1, s.b1, s.w2, s.b2, s.ws, s.bs, bl.C, reinterpret_cast<uint16_t*>(host.data() + o1),
-                      reinterpret_cast<uint16_t*>(host.data() + o2), host.data() + ob1, host.data() + ob2);
-    offs.push_back(o1); offs.push_back(o2); offs.push_back(ob1); offs.push_back(ob2);
+    const size_t o1 = arena.alloc(bl.a1_numel16 / 2, &bl.a1), o2 = arena.alloc(bl.a2_numel16 / 2, &bl.a2);
+    const size_t ob1 = arena.alloc(32 * melgan_mblocks(bl.C), &bl.bias1);
+    const size_t ob2 = arena.alloc(32 * melgan_mblocks(bl.C), &bl.bias2);
+    pack_melgan_block(mode_, s.w1, s.b1, s.w2, s.b2, s.ws, s.bs, bl.C, reinterpret_cast<uint16_t*>(arena.at(o1)),
+                      reinterpret_cast<uint16_t*>(arena.at(o2)), arena.at(ob1), arena.at(ob2));
   }
-  const int64_t otw = take(tail_w_numel), otb = take(cfg.out_channels), og = take(g_numel);
-  std::memcpy(host.data() + otw, tail_w, sizeof(float) * tail_w_numel);
-  std::memcpy(host.data() + otb, tail_b, sizeof(float) * cfg.out_channels);
-  if (g_src) std::memcpy(host.data() + og, g_src, sizeof(float) * g_numel);
-
-  DeviceGuard g(device_);
-  if (hipMalloc(&arena_, (size_t)total * sizeof(float)) != hipSuccess) throw Error(4, "melgan: hipMalloc(weights) failed");
-  if (hipMemcpy(arena_, host.data(), (size_t)total * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(arena_);
-    arena_ = nullptr;
-    throw Error(2, "melgan: copying the weights to the device failed");
-  }
-  size_t oi = 0;
-  pre_.w = arena_ + offs[oi++]; pre_.b = arena_ + offs[oi++];
-  for (auto& u : ups_) { u.w = arena_ + offs[oi++]; u.b = arena_ + offs[oi++]; }
-  for (auto& bl : blocks_) {
-    bl.a1 = arena_ + offs[oi++]; bl.a2 = arena_ + offs[oi++];
-    bl.bias1 = arena_ + offs[oi++]; bl.bias2 = arena_ + offs[oi++];
-  }
-  tail_w_ = arena_ + otw;
-  tail_b_ = arena_ + otb;
-  g_ = g_src ? arena_ + og : nullptr;
+  arena.put(hw[wi], (size_t)cfg.out_channels * (base >> n) * cfg.proj_kernel, &tail_w_);
+  arena.put(hw[wi + 1], cfg.out_channels, &tail_b_);
+  wi += 2;
+  if (cfg.pqmf_bands > 0) arena.put(hw[wi++], (size_t)cfg.pqmf_bands * (cfg.pqmf_taps + 1), &g_);
+  arena.upload(device_, arena_);
   hop_ = 1;
   for (int i = 0; i < n; ++i) hop_ *= cfg.upsample_factors[i];
-}
-
-Melgan::~Melgan() {
-  if (arena_) (void)hipFree(arena_);
-  if (ws_) (void)hipFree(ws_);
 }
 
 int64_t Melgan::out_len(int T, int pad, int synth) const {
@@ -277,17 +205,13 @@ void Melgan::forward(const float* mel, int B, int C, int T, int pad, int synth, 
   (void)out_len(T, pad, synth);  // every length check, on the host, before any launch
   DeviceGuard g(device_);
   const size_t need = (size_t)workspace_bytes(B, T, pad);
-  if (need > ws_bytes_) {
+  if (need > ws_.bytes()) {
     TTS_HIP_CHECK(hipStreamSynchronize(s));
-    if (ws_) (void)hipFree(ws_);
-    ws_ = nullptr;
-    ws_bytes_ = 0;
-    if (hipMalloc(&ws_, need) != hipSuccess) throw Error(4, "melgan: hipMalloc(workspace) failed");
-    ws_bytes_ = need;
+    ws_.grow(device_, need, "workspace");
   }
   const int64_t plane = plane_floats(B, T, pad);
-  float* buf[2] = {ws_, ws_ + plane};
-  float* gat = ws_ + 2 * plane;
+  float* buf[2] = {ws_.as<>(), ws_.as<>() + plane};
+  float* gat = ws_.as<>() + 2 * plane;
   const int P = (cfg_.proj_kernel - 1) / 2;
   const int L0 = T + 2 * pad;
 

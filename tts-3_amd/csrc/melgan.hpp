@@ -77,9 +77,6 @@ void melgan_check_length(const TtsMelganCfg& c, int64_t T, int pad);
 class Melgan {
  public:
   Melgan(const TtsMelganCfg& cfg, const float* const* host_weights, int device);
-  ~Melgan();
-  Melgan(const Melgan&) = delete;
-  Melgan& operator=(const Melgan&) = delete;
   int64_t out_len(int T, int pad, int synth) const;
   int64_t workspace_bytes(int B, int T, int pad) const;
   void forward(const float* mel, int B, int C, int T, int pad, int synth, float* out, hipStream_t s,
@@ -87,18 +84,15 @@ class Melgan {
   int device() const { return device_; }
 
  private:
-  struct Conv {
-    int Cin = 0, Cout = 0, K = 0, tile = 0, n_chunks = 0, U = 0;
-    int64_t w_numel = 0, b_numel = 0;
-    float* w = nullptr;
-    float* b = nullptr;
+  struct Conv : PackedConv {
+    int U = 0;  // upsamplers: the factor (the K = 2 polyphase conv form, Conv1dArgs::ups)
     std::string name;
   };
   struct Block {
     int C = 0, dil = 1;
     int64_t a1_numel16 = 0, a2_numel16 = 0;
-    void* a1 = nullptr;
-    void* a2 = nullptr;
+    float* a1 = nullptr;  // 16-bit fragments (a1_numel16, a2_numel16 units)
+    float* a2 = nullptr;
     float* bias1 = nullptr;
     float* bias2 = nullptr;
     std::string name;
@@ -115,9 +109,7 @@ class Melgan {
   float* tail_w_ = nullptr;
   float* tail_b_ = nullptr;
   float* g_ = nullptr;
-  float* arena_ = nullptr;
-  float* ws_ = nullptr;
-  size_t ws_bytes_ = 0;
+  DeviceBuffer arena_, ws_;
 };
 
 }  // namespace tts

@@ -36,18 +36,9 @@ Stft::Stft(const TtsStftCfg& cfg, const float* h_window, int device) : cfg_(cfg)
   stft_validate(cfg);
   std::vector<uint16_t> packed((size_t)packed_stft_numel16(cfg.math_mode, cfg.n_fft));
   w_exp_ = pack_stft_matrix(cfg.math_mode, h_window, cfg.win_length, cfg.n_fft, packed.data());
-  a_bytes_ = packed.size() * sizeof(uint16_t);
+  a_.grow(device_, packed.size() * sizeof(uint16_t), "the DFT matrix");
   DeviceGuard g(device_);
-  if (hipMalloc(&a_, a_bytes_) != hipSuccess) throw Error(4, "stft: hipMalloc of the DFT matrix failed");
-  if (hipMemcpy(a_, packed.data(), a_bytes_, hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(a_);
-    throw Error(2, "stft: copying the DFT matrix to the device failed");
-  }
-}
-
-Stft::~Stft() {
-  if (a_) (void)hipFree(a_);
-  if (slots_) (void)hipFree(slots_);
+  TTS_HIP_CHECK(hipMemcpy(a_.as<void>(), packed.data(), a_.bytes(), hipMemcpyHostToDevice));
 }
 
 void Stft::forward(const float* wav, int B, int64_t N, int64_t wav_bstride, float* spec, hipStream_t s,
@@ -64,10 +55,10 @@ void Stft::forward(const float* wav, int B, int64_t N, int64_t wav_bstride, floa
 
   StftArgs a{};
   a.wav = wav;
-  a.a = a_;
+  a.a = a_.as<void>();
   a.spec = spec;
   a.wav_bstride = wav_bstride;
-  a.a_bytes = (unsigned)a_bytes_;
+  a.a_bytes = (unsigned)a_.bytes();
   a.N = (int)N;
   a.T = T;
   a.n_fft = n_fft;
@@ -99,23 +90,18 @@ void Stft::forward(const float* wav, int B, int64_t N, int64_t wav_bstride, floa
   const int RS = (int64_t)B * tiles < 512 ? npt : 1;
 
   if (mode == MATH_FP32_F16X3) {
-    if (B > slots_cap_) {
-      if (slots_) (void)hipFree(slots_);
-      slots_ = nullptr;
-      slots_cap_ = 0;
-      if (hipMalloc(&slots_, (size_t)B * 64 * sizeof(unsigned)) != hipSuccess) throw Error(4, "stft: hipMalloc failed");
-      slots_cap_ = B;
-    }
+    slots_.grow(device_, (size_t)B * 64 * sizeof(unsigned), "stft statistics");
+    unsigned* slots = slots_.as<unsigned>();
     run(prof, s, "stft_amax", 0.0, (double)B * N * 4, [&] {
-      TTS_HIP_CHECK(hipMemsetAsync(slots_, 0, (size_t)B * 64 * sizeof(unsigned), s));
-      launch_amax(wav, N, B, slots_, s, wav_bstride);
+      TTS_HIP_CHECK(hipMemsetAsync(slots, 0, (size_t)B * 64 * sizeof(unsigned), s));
+      launch_amax(wav, N, B, slots, s, wav_bstride);
     });
-    a.amax = slots_;
+    a.amax = slots;
   }
   const double bins = n_fft / 2 + 1;
   const std::string name = std::string("stft_") + (mode == MATH_FP32_F16X3 ? "f16x3" : mode == MATH_BF16 ? "bf16" : "fp32x6");
   run(prof, s, name.c_str(), 2.0 * 2.0 * bins * n_fft * (double)T * B,
-      (double)B * ((double)N * 4 + bins * T * 4) + (double)a_bytes_,
+      (double)B * ((double)N * 4 + bins * T * 4) + (double)a_.bytes(),
       [&] { launch_stft(mode, TN, a, B, tiles, RS, s); });
 }
 

@@ -55,9 +55,6 @@ void launch_stft(int mode, int TN, const StftArgs& a, int B, int tiles, int RS, 
 class Stft {
  public:
   Stft(const TtsStftCfg& cfg, const float* h_window, int device);
-  ~Stft();
-  Stft(const Stft&) = delete;
-  Stft& operator=(const Stft&) = delete;
   void forward(const float* wav, int B, int64_t N, int64_t wav_bstride, float* spec, hipStream_t s,
                Profiler* prof = nullptr);
   int device() const { return device_; }
@@ -65,11 +62,9 @@ class Stft {
  private:
   TtsStftCfg cfg_;
   int device_;
-  void* a_ = nullptr;
-  size_t a_bytes_ = 0;
+  DeviceBuffer a_;  // the packed DFT matrix
   int w_exp_ = 0;
-  unsigned* slots_ = nullptr;  // f16x3: [B][64] max-abs slots
-  int slots_cap_ = 0;
+  DeviceBuffer slots_;  // f16x3: [B][64] max-abs slots
 };
 
 }  // namespace tts

@@ -104,9 +104,6 @@ class GlowEncoder {
   // emb_channels: see glow_encoder_weight_shapes (the embedding is scaled by sqrt(emb_channels))
   GlowEncoder(const TtsGlowEncoderCfg& cfg, const float* const* host_weights, int device, bool with_dp = true,
               int emb_channels = 0);
-  ~GlowEncoder();
-  GlowEncoder(const GlowEncoder&) = delete;
-  GlowEncoder& operator=(const GlowEncoder&) = delete;
   // g: [B][c_in_channels] speaker vector (the reference's g [B][c_in][1]), NULL when c_in_channels == 0
   // x_out [B][H][T] (may be NULL): the encoder state before the heads (x * x_mask); logw may be NULL
   // without a duration predictor
@@ -117,11 +114,7 @@ class GlowEncoder {
   int device() const { return device_; }
 
  private:
-  struct Conv {
-    int Cin = 0, Cout = 0, K = 1, tile = 0, n_chunks = 0, dil = 1, pad = 0;
-    float* w = nullptr;
-    float* b = nullptr;
-  };
+  using Conv = PackedConv;
   struct Affine {  // BatchNorm (eval) as y = x * scale + shift
     float* scale = nullptr;
     float* shift = nullptr;
@@ -163,9 +156,7 @@ class GlowEncoder {
   std::vector<TdsLayer> tds_;
   Conv proj_m_, proj_s_, dp1_, dp2_, dp_proj_;
   Norm dpn1_, dpn2_;
-  float* arena_ = nullptr;
-  float* ws_ = nullptr;
-  size_t ws_bytes_ = 0;
+  DeviceBuffer arena_, ws_;
 };
 
 // ---------------------------------------------------------------------------------------
@@ -195,9 +186,6 @@ void vits_sdp_validate(const TtsVitsSdpCfg& c);
 class VitsSdp {
  public:
   VitsSdp(const TtsVitsSdpCfg& cfg, const float* const* host_weights, int device);
-  ~VitsSdp();
-  VitsSdp(const VitsSdp&) = delete;
-  VitsSdp& operator=(const VitsSdp&) = delete;
   // logw [B][1][T] = StochasticDurationPredictor(x, x_mask, g, reverse=True, noise_scale) with the
   // standard normal draw noise [B][2][T] given (stochastic_duration_predictor.py:256-282)
   // lang [B][language_emb_dim] or NULL (cond_lang, :253-254)
@@ -206,11 +194,7 @@ class VitsSdp {
   int device() const { return device_; }
 
  private:
-  struct Conv {
-    int Cin = 0, Cout = 0, tile = 0, n_chunks = 0;
-    float* w = nullptr;
-    float* b = nullptr;
-  };
+  using Conv = PackedConv;
   struct Dds {  // DilatedDepthSeparableConv, 3 layers
     float* sep_w[3] = {};
     float* sep_b[3] = {};
@@ -237,9 +221,7 @@ class VitsSdp {
   float* cond_b_ = nullptr;
   float* lang_w_ = nullptr;      // cond_lang [H][L], bias [H]
   float* lang_b_ = nullptr;
-  float* arena_ = nullptr;
-  float* ws_ = nullptr;
-  size_t ws_bytes_ = 0;
+  DeviceBuffer arena_, ws_;
 };
 
 // The deterministic DurationPredictor of VITS with use_sdp=False (vits.py:694-702,
@@ -251,19 +233,12 @@ void vits_dp_validate(const TtsVitsDpCfg& c);
 class VitsDp {
  public:
   VitsDp(const TtsVitsDpCfg& cfg, const float* const* host_weights, int device);
-  ~VitsDp();
-  VitsDp(const VitsDp&) = delete;
-  VitsDp& operator=(const VitsDp&) = delete;
   void forward(const float* x, const float* x_mask, const float* g, const float* lang, int B, int T, float* logw,
                hipStream_t s, Profiler* prof = nullptr);
   int device() const { return device_; }
 
  private:
-  struct Conv {
-    int Cin = 0, Cout = 0, K = 1, tile = 0, n_chunks = 0;
-    float* w = nullptr;
-    float* b = nullptr;
-  };
+  using Conv = PackedConv;
   void reserve(int B, int T);
 
   TtsVitsDpCfg cfg_;
@@ -271,9 +246,7 @@ class VitsDp {
   Conv c1_, c2_, proj_;
   float *n1g_ = nullptr, *n1b_ = nullptr, *n2g_ = nullptr, *n2b_ = nullptr;
   float *cond_w_ = nullptr, *cond_b_ = nullptr, *lang_w_ = nullptr, *lang_b_ = nullptr;
-  float* arena_ = nullptr;
-  float* ws_ = nullptr;
-  size_t ws_bytes_ = 0;
+  DeviceBuffer arena_, ws_;
 };
 
 }  // namespace tts

@@ -13,8 +13,6 @@
 // (:98-99, :103-107) is a per-(utterance, channel) vector added in the in-layer epilogue.
 #include "vits.hpp"
 
-#include <cstring>
-
 #include "glow.hpp"
 
 namespace tts {
@@ -79,39 +77,9 @@ VitsFlow::VitsFlow(const TtsVitsFlowCfg& cfg, const float* const* hw, int device
   const int F = cfg_.num_flows;
   const int mode = cfg_.math_mode;
 
-  std::vector<float> host;
-  auto align = [](size_t n) { return (n + 63) & ~size_t(63); };
-  std::vector<std::pair<size_t, float**>> fix;
-  auto put_raw = [&](const float* src, size_t n, float** dst) {
-    const size_t off = host.size();
-    host.resize(off + align(n), 0.f);
-    std::memcpy(host.data() + off, src, n * sizeof(float));
-    fix.push_back({off, dst});
-  };
-  std::vector<float> wperm, bperm;
-  auto put_conv = [&](Conv& cv, const float* w, const float* b, int Cin, int Cout, int K, int dil,
-                      bool gate = false) {
-    cv.Cin = Cin; cv.Cout = Cout; cv.K = K; cv.dil = dil;
-    cv.tile = flow_conv_tile(mode, Cout, K, Cin, dil);
-    cv.gated = gate && flow_gate_fused(mode, Cout / 2, K, dil);
-    if (cv.gated) {
-      gate_permute_rows(w, b, Cout / 2, Cin, K, wperm, bperm);
-      w = wperm.data();
-      b = bperm.data();
-      cv.tile = kSplitGateTile;
-    }
-    const ConvTile t = conv_tile(mode, cv.tile);
-    cv.n_chunks = ceil_div(Cin, t.CK);
-    const size_t n = packed_conv_numel(mode, Cout, Cin, K, t);
-    const size_t off = host.size();
-    host.resize(off + align(n), 0.f);
-    cv.w_exp = pack_conv(mode, w, Cout, Cin, K, t, host.data() + off);
-    fix.push_back({off, &cv.w});
-    const size_t nb = (size_t)ceil_div(Cout, t.BM) * t.BM;
-    const size_t offb = host.size();
-    host.resize(offb + align(nb), 0.f);
-    std::memcpy(host.data() + offb, b, Cout * sizeof(float));
-    fix.push_back({offb, &cv.b});
+  HostArena arena;
+  auto put_conv = [&](Conv& cv, const float* w, const float* b, int Cin, int Cout, int K, int dil, bool gate = false) {
+    put_flow_conv(arena, cv, mode, w, b, Cin, Cout, K, dil, gate);
   };
 
   flows_.resize(F);
@@ -142,8 +110,8 @@ VitsFlow::VitsFlow(const TtsVitsFlowCfg& cfg, const float* const* hw, int device
       wi += 2;
     }
     if (cfg_.cond_channels > 0) {
-      put_raw(hw[wi], (size_t)2 * H * L * cfg_.cond_channels, &Fl.cond_w);
-      put_raw(hw[wi + 1], (size_t)2 * H * L, &Fl.cond_b);
+      arena.put(hw[wi], (size_t)2 * H * L * cfg_.cond_channels, &Fl.cond_w);
+      arena.put(hw[wi + 1], (size_t)2 * H * L, &Fl.cond_b);
       wi += 2;
     }
     {  // post, negated (reverse) and as is (forward); row s of the updated half is logical
@@ -160,15 +128,7 @@ VitsFlow::VitsFlow(const TtsVitsFlowCfg& cfg, const float* const* hw, int device
       wi += 2;
     }
   }
-  if (hipMalloc(&arena_, host.size() * sizeof(float)) != hipSuccess) throw Error(4, "hipMalloc(weights) failed");
-  TTS_HIP_CHECK(hipMemcpy(arena_, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
-  for (auto& p : fix) *p.second = arena_ + p.first;
-}
-
-VitsFlow::~VitsFlow() {
-  DeviceGuard g(device_);
-  if (arena_) (void)hipFree(arena_);
-  if (ws_) (void)hipFree(ws_);
+  arena.upload(device_, arena_);
 }
 
 // f16x3 statistics: per flow (execution order) 2L + 2 groups of [B][64] slots: pre's input half,
@@ -185,10 +145,7 @@ void VitsFlow::reserve(int B, int T) {
   const size_t odd = (cfg_.num_flows & 1) ? plane * cfg_.channels + 64 : 0;
   const size_t need =
       (plane * 7 * H + (size_t)B * 2 * H * cfg_.num_layers + 64 * 8 + odd + amax_floats(B) + 64) * sizeof(float);
-  if (need <= ws_bytes_) return;
-  if (ws_) { TTS_HIP_CHECK(hipFree(ws_)); ws_ = nullptr; ws_bytes_ = 0; }
-  if (hipMalloc(&ws_, need) != hipSuccess) throw Error(4, "hipMalloc(workspace) failed");
-  ws_bytes_ = need;
+  ws_.grow(device_, need, "workspace");
 }
 
 void VitsFlow::reverse(const float* x, const float* mask, const float* g, int B, int C, int T, float* y,
@@ -217,7 +174,7 @@ void VitsFlow::run_flows(bool rev, const float* x, const float* mask, const floa
   const int L = cfg_.num_layers;
   const size_t plane = (size_t)B * T;
   auto al = [](size_t n) { return (n + 63) & ~size_t(63); };
-  float* p = ws_;
+  float* p = ws_.as<>();
   float* hb = p; p += al(plane * H);
   float* xin = p; p += al(plane * 2 * H);
   float* acts = p; p += al(plane * H);
@@ -391,38 +348,9 @@ VitsPosterior::VitsPosterior(const TtsVitsPosteriorCfg& cfg, const float* const*
   const int H = cfg_.hidden_channels;
   const int L = cfg_.num_layers;
   const int mode = cfg_.math_mode;
-  std::vector<float> host;
-  auto align = [](size_t n) { return (n + 63) & ~size_t(63); };
-  std::vector<std::pair<size_t, float**>> fix;
-  auto put_raw = [&](const float* src, size_t n, float** dst) {
-    const size_t off = host.size();
-    host.resize(off + align(n), 0.f);
-    std::memcpy(host.data() + off, src, n * sizeof(float));
-    fix.push_back({off, dst});
-  };
-  std::vector<float> wperm, bperm;
+  HostArena arena;
   auto put_conv = [&](Conv& cv, const float* w, const float* b, int Cin, int Cout, int K, int dil, bool gate = false) {
-    cv.Cin = Cin; cv.Cout = Cout; cv.K = K; cv.dil = dil;
-    cv.tile = flow_conv_tile(mode, Cout, K, Cin, dil);
-    cv.gated = gate && flow_gate_fused(mode, Cout / 2, K, dil);
-    if (cv.gated) {
-      gate_permute_rows(w, b, Cout / 2, Cin, K, wperm, bperm);
-      w = wperm.data();
-      b = bperm.data();
-      cv.tile = kSplitGateTile;
-    }
-    const ConvTile t = conv_tile(mode, cv.tile);
-    cv.n_chunks = ceil_div(Cin, t.CK);
-    const size_t n = packed_conv_numel(mode, Cout, Cin, K, t);
-    const size_t off = host.size();
-    host.resize(off + align(n), 0.f);
-    cv.w_exp = pack_conv(mode, w, Cout, Cin, K, t, host.data() + off);
-    fix.push_back({off, &cv.w});
-    const size_t nb = (size_t)ceil_div(Cout, t.BM) * t.BM;
-    const size_t offb = host.size();
-    host.resize(offb + align(nb), 0.f);
-    std::memcpy(host.data() + offb, b, Cout * sizeof(float));
-    fix.push_back({offb, &cv.b});
+    put_flow_conv(arena, cv, mode, w, b, Cin, Cout, K, dil, gate);
   };
   size_t wi = 0;
   put_conv(pre_, hw[0], hw[1], cfg_.in_channels, H, 1, 1);
@@ -436,20 +364,12 @@ VitsPosterior::VitsPosterior(const TtsVitsPosteriorCfg& cfg, const float* const*
   }
   for (int l = 0; l < L; ++l, wi += 2) put_conv(res_skip_[l], hw[wi], hw[wi + 1], H, (l < L - 1) ? 2 * H : H, 1, 1);
   if (cfg_.cond_channels > 0) {
-    put_raw(hw[wi], (size_t)2 * H * L * cfg_.cond_channels, &cond_w_);
-    put_raw(hw[wi + 1], (size_t)2 * H * L, &cond_b_);
+    arena.put(hw[wi], (size_t)2 * H * L * cfg_.cond_channels, &cond_w_);
+    arena.put(hw[wi + 1], (size_t)2 * H * L, &cond_b_);
     wi += 2;
   }
   put_conv(proj_, hw[wi], hw[wi + 1], H, 2 * cfg_.out_channels, 1, 1);
-  if (hipMalloc(&arena_, host.size() * sizeof(float)) != hipSuccess) throw Error(4, "hipMalloc(weights) failed");
-  TTS_HIP_CHECK(hipMemcpy(arena_, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
-  for (auto& p : fix) *p.second = arena_ + p.first;
-}
-
-VitsPosterior::~VitsPosterior() {
-  DeviceGuard g(device_);
-  if (arena_) (void)hipFree(arena_);
-  if (ws_) (void)hipFree(ws_);
+  arena.upload(device_, arena_);
 }
 
 // f16x3 statistics: the input spectrogram, h before each in_layer, acts before each res_skip,
@@ -465,10 +385,7 @@ void VitsPosterior::reserve(int B, int T) {
   // h H, xin 2H, acts H, rs 2H, skip H, stats 2 out; cond vectors [B][2HL]
   const size_t need = (plane * (7 * H + 2 * cfg_.out_channels) + (size_t)B * 2 * H * cfg_.num_layers + 64 * 8 +
                        amax_floats(B) + 64) * sizeof(float);
-  if (need <= ws_bytes_) return;
-  if (ws_) { TTS_HIP_CHECK(hipFree(ws_)); ws_ = nullptr; ws_bytes_ = 0; }
-  if (hipMalloc(&ws_, need) != hipSuccess) throw Error(4, "hipMalloc(workspace) failed");
-  ws_bytes_ = need;
+  ws_.grow(device_, need, "workspace");
 }
 
 void VitsPosterior::forward(const float* x, const float* mask, const float* g, const float* eps, int B, int C, int T,
@@ -485,7 +402,7 @@ void VitsPosterior::forward(const float* x, const float* mask, const float* g, c
   const int Co = cfg_.out_channels;
   const size_t plane = (size_t)B * T;
   auto al = [](size_t n) { return (n + 63) & ~size_t(63); };
-  float* p = ws_;
+  float* p = ws_.as<>();
   float* hb = p; p += al(plane * H);
   float* xin = p; p += al(plane * 2 * H);
   float* acts = p; p += al(plane * H);

@@ -16,9 +16,6 @@ void vits_flow_validate(const TtsVitsFlowCfg& c);
 class VitsFlow {
  public:
   VitsFlow(const TtsVitsFlowCfg& cfg, const float* const* host_weights, int device);
-  ~VitsFlow();
-  VitsFlow(const VitsFlow&) = delete;
-  VitsFlow& operator=(const VitsFlow&) = delete;
   void reverse(const float* x, const float* mask, const float* g, int B, int C, int T, float* y, hipStream_t s,
                Profiler* prof = nullptr);
   // reverse=False (networks.py:225-228): for flow in flows: x = flow(x); x = flip(x)
@@ -27,12 +24,7 @@ class VitsFlow {
   int device() const { return device_; }
 
  private:
-  struct Conv {
-    int Cin = 0, Cout = 0, K = 1, dil = 1, tile = 0, n_chunks = 0, w_exp = 0;
-    bool gated = false;  // in_layer with the WN gate fused (kSplitGateTile)
-    float* w = nullptr;
-    float* b = nullptr;
-  };
+  using Conv = PackedConv;
   struct Flow {
     Conv pre, post;  // pre/post already permuted for the flip parity this flow runs at; post negated
     Conv post_fwd;   // the same rows, not negated (forward direction: x1 = m + x1 * mask)
@@ -50,9 +42,7 @@ class VitsFlow {
   TtsVitsFlowCfg cfg_;
   int device_;
   std::vector<Flow> flows_;
-  float* arena_ = nullptr;
-  float* ws_ = nullptr;
-  size_t ws_bytes_ = 0;
+  DeviceBuffer arena_, ws_;
   bool amax_prepass_ = false;
   bool wn_fused_ = false;  // res_skip conv + WN update in one launch (flow_wn_fused)
   bool wn_layer_ = false;  // every WN layer in one launch (launch_glow_wn_layer, flow_wn_layer)
@@ -68,20 +58,12 @@ void launch_posterior_sample(const float* stats, const float* eps, const float* 
 class VitsPosterior {
  public:
   VitsPosterior(const TtsVitsPosteriorCfg& cfg, const float* const* host_weights, int device);
-  ~VitsPosterior();
-  VitsPosterior(const VitsPosterior&) = delete;
-  VitsPosterior& operator=(const VitsPosterior&) = delete;
   void forward(const float* x, const float* mask, const float* g, const float* eps, int B, int C, int T, float* z,
                float* m, float* logs, hipStream_t s, Profiler* prof = nullptr);
   int device() const { return device_; }
 
  private:
-  struct Conv {
-    int Cin = 0, Cout = 0, K = 1, dil = 1, tile = 0, n_chunks = 0, w_exp = 0;
-    bool gated = false;
-    float* w = nullptr;
-    float* b = nullptr;
-  };
+  using Conv = PackedConv;
   void reserve(int B, int T);
   size_t amax_floats(int B) const;
 
@@ -92,9 +74,7 @@ class VitsPosterior {
   bool wn_layer_ = false;  // every WN layer in one launch (launch_glow_wn_layer, flow_wn_layer)
   float* cond_w_ = nullptr;
   float* cond_b_ = nullptr;
-  float* arena_ = nullptr;
-  float* ws_ = nullptr;
-  size_t ws_bytes_ = 0;
+  DeviceBuffer arena_, ws_;
 };
 
 }  // namespace tts

@@ -6,7 +6,6 @@
 //   its 1x1 convs on the conv kernels, the depthwise conv + LayerNorm2 + gelu stages, the spline and
 //   the affine flow on kernels_vits_text.hip.
 #include <cmath>
-#include <cstring>
 
 #include "text.hpp"
 
@@ -134,47 +133,34 @@ VitsSdp::VitsSdp(const TtsVitsSdpCfg& cfg, const float* const* hw, int device) :
   for (size_t i = 0; i < shapes.size(); ++i)
     TTS_REQUIRE(hw[i] != nullptr, 1, "weight pointer " + std::to_string(i) + " is NULL");
   const int H = cfg_.hidden_channels, k = cfg_.kernel_size, mode = cfg_.math_mode;
-  std::vector<float> host;
-  std::vector<std::pair<size_t, float**>> fix;
-  auto align = [](size_t n) { return (n + 63) & ~size_t(63); };
-  auto put = [&](const float* src, size_t n, float** dst) {
-    const size_t off = host.size();
-    host.resize(off + align(n), 0.f);
-    std::memcpy(host.data() + off, src, n * sizeof(float));
-    fix.push_back({off, dst});
-  };
+  HostArena arena;
   auto put_conv = [&](Conv& cv, const float* w, const float* b, int Cout, int Cin) {
     cv.Cin = Cin; cv.Cout = Cout;
     // short text batches: the split modes take the 32x128 tile, as the Glow encoder does
     cv.tile = is_split_mode(mode) ? 16 : conv_tile_for(mode, Cout, 1, Cin, 1, false);
-    const ConvTile t = conv_tile(mode, cv.tile);
-    cv.n_chunks = ceil_div(Cin, t.CK);
-    const size_t n = packed_conv_numel(mode, Cout, Cin, 1, t);
-    const size_t off = host.size();
-    host.resize(off + align(n), 0.f);
-    TTS_REQUIRE(pack_conv(mode, w, Cout, Cin, 1, t, host.data() + off) == 0, 3, "SDP: scaled packing unsupported");
-    fix.push_back({off, &cv.w});
-    const size_t nb = (size_t)ceil_div(Cout, t.BM) * t.BM;
-    const size_t offb = host.size();
-    host.resize(offb + align(nb), 0.f);
-    std::memcpy(host.data() + offb, b, Cout * sizeof(float));
-    fix.push_back({offb, &cv.b});
+    TTS_REQUIRE(arena.put_conv(cv, mode, conv_tile(mode, cv.tile), w, b) == 0, 3, "SDP: scaled packing unsupported");
   };
   size_t wi = 0;
   auto put_dds = [&](Dds& d) {
     for (int i = 0; i < kDdsLayers; ++i) {
-      put(hw[wi], (size_t)H * k, &d.sep_w[i]);
-      put(hw[wi + 1], H, &d.sep_b[i]);
+      arena.put(hw[wi], (size_t)H * k, &d.sep_w[i]);
+      arena.put(hw[wi + 1], H, &d.sep_b[i]);
       wi += 2;
     }
     for (int i = 0; i < kDdsLayers; ++i) { put_conv(d.c1x1[i], hw[wi], hw[wi + 1], H, H); wi += 2; }
-    for (int i = 0; i < kDdsLayers; ++i) { put(hw[wi], H, &d.n1g[i]); put(hw[wi + 1], H, &d.n1b[i]); wi += 2; }
-    for (int i = 0; i < kDdsLayers; ++i) { put(hw[wi], H, &d.n2g[i]); put(hw[wi + 1], H, &d.n2b[i]); wi += 2; }
+    for (int i = 0; i < kDdsLayers; ++i, wi += 2) {
+      arena.put(hw[wi], H, &d.n1g[i]);
+      arena.put(hw[wi + 1], H, &d.n1b[i]);
+    }
+    for (int i = 0; i < kDdsLayers; ++i, wi += 2) {
+      arena.put(hw[wi], H, &d.n2g[i]);
+      arena.put(hw[wi + 1], H, &d.n2b[i]);
+    }
   };
   put_conv(pre_, hw[wi], hw[wi + 1], H, cfg_.in_channels); wi += 2;
   put_dds(dds_);
   put_conv(proj_, hw[wi], hw[wi + 1], H, H); wi += 2;
-  put(hw[wi], 2, &ea_tr_); put(hw[wi + 1], 2, &ea_ls_); wi += 2;
+  arena.put(hw[wi], 2, &ea_tr_); arena.put(hw[wi + 1], 2, &ea_ls_); wi += 2;
   flows_.resize(cfg_.num_flows);
   for (auto& F : flows_) {
     put_conv(F.pre, hw[wi], hw[wi + 1], H, 1); wi += 2;
@@ -182,25 +168,17 @@ VitsSdp::VitsSdp(const TtsVitsSdpCfg& cfg, const float* const* hw, int device) :
     put_conv(F.proj, hw[wi], hw[wi + 1], 3 * kSdpBins - 1, H); wi += 2;
   }
   if (cfg_.cond_channels > 0) {
-    put(hw[wi], (size_t)H * cfg_.cond_channels, &cond_w_);
-    put(hw[wi + 1], H, &cond_b_);
+    arena.put(hw[wi], (size_t)H * cfg_.cond_channels, &cond_w_);
+    arena.put(hw[wi + 1], H, &cond_b_);
     wi += 2;
   }
   if (cfg_.language_emb_dim > 0) {
-    put(hw[wi], (size_t)H * cfg_.language_emb_dim, &lang_w_);
-    put(hw[wi + 1], H, &lang_b_);
+    arena.put(hw[wi], (size_t)H * cfg_.language_emb_dim, &lang_w_);
+    arena.put(hw[wi + 1], H, &lang_b_);
     wi += 2;
   }
   TTS_REQUIRE(wi == shapes.size(), 2, "internal: SDP weight count mismatch");
-  if (hipMalloc(&arena_, host.size() * sizeof(float)) != hipSuccess) throw Error(4, "hipMalloc(weights) failed");
-  TTS_HIP_CHECK(hipMemcpy(arena_, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
-  for (auto& p : fix) *p.second = arena_ + p.first;
-}
-
-VitsSdp::~VitsSdp() {
-  DeviceGuard g(device_);
-  if (arena_) (void)hipFree(arena_);
-  if (ws_) (void)hipFree(ws_);
+  arena.upload(device_, arena_);
 }
 
 void VitsSdp::reserve(int B, int T) {
@@ -208,10 +186,7 @@ void VitsSdp::reserve(int B, int T) {
   const int H = cfg_.hidden_channels;
   // xs, h, a, u [H]; hp [29]; z [2]; cond vectors [2][B][H]
   const size_t need = (plane * (4 * (size_t)H + 3 * kSdpBins - 1 + 2) + 2 * (size_t)B * H + 8 * 64) * sizeof(float);
-  if (need <= ws_bytes_) return;
-  if (ws_) { TTS_HIP_CHECK(hipFree(ws_)); ws_ = nullptr; ws_bytes_ = 0; }
-  if (hipMalloc(&ws_, need) != hipSuccess) throw Error(4, "hipMalloc(workspace) failed");
-  ws_bytes_ = need;
+  ws_.grow(device_, need, "workspace");
 }
 
 void VitsSdp::reverse(const float* x, const float* x_mask, const float* g, const float* lang, const float* noise,
@@ -227,7 +202,7 @@ void VitsSdp::reverse(const float* x, const float* x_mask, const float* g, const
   const size_t plane = (size_t)B * T;
   const double P = (double)plane;
   auto al = [](size_t n) { return (n + 63) & ~size_t(63); };
-  float* p = ws_;
+  float* p = ws_.as<>();
   float* xs = p; p += al(plane * H);   // the SDP's conditioning x (proj(DDS(pre(x) + cond(g))) * mask)
   float* h = p; p += al(plane * H);    // a DDS state
   float* a = p; p += al(plane * H);    // depthwise-conv stage output
@@ -331,56 +306,29 @@ VitsDp::VitsDp(const TtsVitsDpCfg& cfg, const float* const* hw, int device) : cf
     TTS_REQUIRE(hw[i] != nullptr, 1, "weight pointer " + std::to_string(i) + " is NULL");
   const int I = cfg_.in_channels + cfg_.language_emb_dim, F = cfg_.hidden_channels, k = cfg_.kernel_size;
   const int mode = cfg_.math_mode;
-  std::vector<float> host;
-  std::vector<std::pair<size_t, float**>> fix;
-  auto align = [](size_t n) { return (n + 63) & ~size_t(63); };
-  auto put = [&](const float* src, size_t n, float** dst) {
-    const size_t off = host.size();
-    host.resize(off + align(n), 0.f);
-    std::memcpy(host.data() + off, src, n * sizeof(float));
-    fix.push_back({off, dst});
-  };
+  HostArena arena;
   auto put_conv = [&](Conv& cv, const float* w, const float* b, int Cout, int Cin, int K) {
     cv.Cin = Cin; cv.Cout = Cout; cv.K = K;
     // text batches are short: the split modes take the 32x128 tile, as the Glow encoder does
     cv.tile = is_split_mode(mode) ? 16 : conv_tile_for(mode, Cout, K, Cin, 1, false);
-    const ConvTile t = conv_tile(mode, cv.tile);
-    cv.n_chunks = ceil_div(Cin, t.CK);
-    const size_t n = packed_conv_numel(mode, Cout, Cin, K, t);
-    const size_t off = host.size();
-    host.resize(off + align(n), 0.f);
-    TTS_REQUIRE(pack_conv(mode, w, Cout, Cin, K, t, host.data() + off) == 0, 3, "DP: scaled packing unsupported");
-    fix.push_back({off, &cv.w});
-    const size_t nb = (size_t)ceil_div(Cout, t.BM) * t.BM;
-    const size_t offb = host.size();
-    host.resize(offb + align(nb), 0.f);
-    std::memcpy(host.data() + offb, b, Cout * sizeof(float));
-    fix.push_back({offb, &cv.b});
+    TTS_REQUIRE(arena.put_conv(cv, mode, conv_tile(mode, cv.tile), w, b) == 0, 3, "DP: scaled packing unsupported");
   };
   put_conv(c1_, hw[0], hw[1], F, I, k);
-  put(hw[2], F, &n1g_); put(hw[3], F, &n1b_);
+  arena.put(hw[2], F, &n1g_); arena.put(hw[3], F, &n1b_);
   put_conv(c2_, hw[4], hw[5], F, F, k);
-  put(hw[6], F, &n2g_); put(hw[7], F, &n2b_);
+  arena.put(hw[6], F, &n2g_); arena.put(hw[7], F, &n2b_);
   put_conv(proj_, hw[8], hw[9], 1, F, 1);
   size_t wi = 10;
   if (cfg_.cond_channels > 0) {
-    put(hw[wi], (size_t)I * cfg_.cond_channels, &cond_w_); put(hw[wi + 1], I, &cond_b_);
+    arena.put(hw[wi], (size_t)I * cfg_.cond_channels, &cond_w_); arena.put(hw[wi + 1], I, &cond_b_);
     wi += 2;
   }
   if (cfg_.language_emb_dim > 0) {
-    put(hw[wi], (size_t)I * cfg_.language_emb_dim, &lang_w_); put(hw[wi + 1], I, &lang_b_);
+    arena.put(hw[wi], (size_t)I * cfg_.language_emb_dim, &lang_w_); arena.put(hw[wi + 1], I, &lang_b_);
     wi += 2;
   }
   TTS_REQUIRE(wi == shapes.size(), 2, "internal: DP weight count mismatch");
-  if (hipMalloc(&arena_, host.size() * sizeof(float)) != hipSuccess) throw Error(4, "hipMalloc(weights) failed");
-  TTS_HIP_CHECK(hipMemcpy(arena_, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
-  for (auto& p : fix) *p.second = arena_ + p.first;
-}
-
-VitsDp::~VitsDp() {
-  DeviceGuard g(device_);
-  if (arena_) (void)hipFree(arena_);
-  if (ws_) (void)hipFree(ws_);
+  arena.upload(device_, arena_);
 }
 
 void VitsDp::reserve(int B, int T) {
@@ -388,10 +336,7 @@ void VitsDp::reserve(int B, int T) {
   const size_t I = (size_t)cfg_.in_channels + cfg_.language_emb_dim, F = cfg_.hidden_channels;
   // xin [I]; h, n [F]; cond vectors [2][B][I]
   const size_t need = (plane * (I + 2 * F) + 2 * (size_t)B * I + 5 * 64) * sizeof(float);
-  if (need <= ws_bytes_) return;
-  if (ws_) { TTS_HIP_CHECK(hipFree(ws_)); ws_ = nullptr; ws_bytes_ = 0; }
-  if (hipMalloc(&ws_, need) != hipSuccess) throw Error(4, "hipMalloc(workspace) failed");
-  ws_bytes_ = need;
+  ws_.grow(device_, need, "workspace");
 }
 
 void VitsDp::forward(const float* x, const float* x_mask, const float* g, const float* lang, int B, int T,
@@ -407,7 +352,7 @@ void VitsDp::forward(const float* x, const float* x_mask, const float* g, const 
   const size_t plane = (size_t)B * T;
   const double P = (double)plane;
   auto al = [](size_t n) { return (n + 63) & ~size_t(63); };
-  float* p = ws_;
+  float* p = ws_.as<>();
   float* xin = p; p += al(plane * I);
   float* h = p; p += al(plane * F);
   float* nb = p; p += al(plane * F);
