@@ -582,9 +582,12 @@ void launch_res3_t(const ResBlock3Args& a, int B, hipStream_t s) {
 template <class S>
 void launch_res3_s(const ResBlock3Args& a, int B, int C, int K, hipStream_t s) {
   // C = 64: 128 columns (2 waves/SIMD, a quarter of the columns are halo; 192 columns at one
-  // wave per SIMD measured slower).  C = 128: 128 columns as 8 waves of 32 rows x 64 columns (two
-  // per SIMD; 2 x 2 waves of 64 x 64 measured slower); LDS 8 x 138 rows.  Kernels 7 / 11 (32 and
-  // 64 channels): the 256-column tile keeps 184 / 136 columns
+  // wave per SIMD measured slower).  C = 128: 128 columns, LDS 8 x 138 rows.  The two-piece scheme
+  // (f16x3) takes GEO 4: 4 waves of 64 rows x 64 columns on swizzled 64-byte rows, 73,760 B, two
+  // workgroups per CU (4.28 ms per batch against 4.73 ms for GEO 3, same bits).  bf16 keeps GEO 3,
+  // 8 waves of 32 rows x 64 columns, two per SIMD in one workgroup (its 48-byte rows already fit
+  // twice; not re-measured).  Kernels 7 / 11 (32 and 64 channels): the 256-column tile keeps
+  // 184 / 136 columns
   if (K == 7) {
     if (C == 32) launch_res3_t<S, 32, 0, 7>(a, B, s);
     else launch_res3_t<S, 64, 0, 7>(a, B, s);
@@ -597,14 +600,16 @@ void launch_res3_s(const ResBlock3Args& a, int B, int C, int K, hipStream_t s) {
   }
   if (C == 32) launch_res3_t<S, 32, 0, 3>(a, B, s);
   else if (C == 128) {
-    if constexpr (S::ROWB <= 80) launch_res3_t<S, 128, 3, 3>(a, B, s);
+    if constexpr (S::NP == 2) launch_res3_t<S, 128, 4, 3>(a, B, s);
+    else if constexpr (S::ROWB <= 80) launch_res3_t<S, 128, 3, 3>(a, B, s);
     else throw Error(3, "resblock3: 128 channels need a split scheme of at most 80-byte rows");
   } else launch_res3_t<S, 64, 2, 3>(a, B, s);
 }
 }  // namespace
 
 bool resblock3_supported(int mode, int C, int K, const int* dil) {
-  // C = 128 stages 8 groups x 138 rows: 88 KB of LDS for f16x3 / 53 KB for bf16 (x6 is not built);
+  // C = 128 stages 8 groups x 138 rows: 71 KB of LDS for f16x3 (64-byte swizzled rows, two
+  // workgroups per CU) / 53 KB for bf16 (x6 is not built);
   // kernels 7 / 11 at 32 / 64 channels (256-column tiles)
   if (!is_split_mode(mode)) return false;
   if (K == 3) {

@@ -18,6 +18,7 @@
 #pragma once
 #include <type_traits>
 
+#include "res3_layout.hpp"
 #include "split_device.hpp"
 
 #ifndef RES_PD_B1
@@ -48,7 +49,13 @@ constexpr int rb2_halo(int K) { return K == 3 ? 4 : (K == 5 ? 12 : (K == 7 ? 9 :
 
 // GEO 0: 256 columns, 4 waves side by side; GEO 1 / 2: 192 / 128 columns, 2 x 2 waves;
 // GEO 3: 128 columns, 8 waves (4 row blocks x 2 column halves at C = 128, two waves per SIMD).
-// Measured (f16x3, per batch): C = 128 GEO 3 5.0 ms vs GEO 2 5.5 ms; 8-wave forms at C = 64
+// GEO 4: the tiles of GEO 2 / 3 (128 columns, 2 x 2 waves; at C = 128 a wave owns 64 rows x 64
+// columns) on the swizzled 64-byte rows of res3_layout.hpp and two waves per SIMD asked of the
+// compiler.  At C = 128 the two-piece scheme then stages 8 x 138 x 64 = 70,656 B instead of the
+// 88,320 B of the padded 80-byte rows, so two workgroups share a CU and drift out of phase: one
+// runs MFMAs while the other sits in its prologue, epilogue or barriers.
+// Measured (f16x3, per batch): C = 128 GEO 4 4.28 ms vs GEO 3 4.73 ms, bitwise the same output
+// (profiles/ab_block_c128_2wg.txt; earlier, GEO 3 5.0 ms vs GEO 2 5.5 ms); 8-wave forms at C = 64
 // (256 columns) and C = 32 (512 columns) were slower than GEO 2 / GEO 0 (+0.2 / +0.3 ms).
 template <class S, int C, int GEO, int K = 3, int NCV = 6, int XO = R3_XOFF, int LEAD = R3_LEAD>
 struct Res3Cfg {
@@ -62,7 +69,15 @@ struct Res3Cfg {
   static constexpr int TN = RP_W / 32 / WN;
   static constexpr int NC = C / 16;
   static constexpr int PR = RP_W + 2 * XO;  // rows per group (X: RP_W + 2 XO, xt: RP_W + K - 1)
-  static constexpr int LDSB = NC * PR * S::ROWB;
+  // row pitch and the place of a 16-byte unit inside a row: every LDS address of the kernel's
+  // staged operands is ROWS::off(row, unit), unit = half + 2 piece (+ 8 bytes for the second
+  // channel quad of a unit in the prologue's 8-byte stores)
+  using ROWS = Res3Rows<S::NP, GEO == 4 && S::NP == 2>;
+  static_assert(GEO == 4 || ROWS::PITCH == S::ROWB, "the padded layout is the scheme's own row");
+  static constexpr int LDSB = NC * PR * ROWS::PITCH;
+  // with red and bsm: what a workgroup takes of the CU's 160 KB
+  static constexpr int LDS_TOTAL = LDSB + 2 * NW * 4 + NCV * C * 4;
+  static_assert(GEO != 4 || LDS_TOTAL <= 80 * 1024, "GEO 4: two workgroups per CU");
   static_assert(TM >= 1 && TM * WM * 32 == C && TN * WN * 32 == RP_W, "geometry");
 };
 
@@ -76,12 +91,13 @@ struct Res3Cfg {
 template <class S, int C, int GEO, int K, int NCV, int XO, int LEAD, int PL = 0>
 __global__ __launch_bounds__((Res3Cfg<S, C, GEO, K, NCV, XO, LEAD>::NT))
 __attribute__((amdgpu_waves_per_eu(S::NP == 1 && RB3_W_B1 > 0 ? RB3_W_B1
-                                                                : (C == 64 && GEO == 2 ? RB3_W64 : (C == 32 || GEO == 3 ? 2 : 1)))))
+                                                                : (C == 64 && GEO == 2 ? RB3_W64 : (C == 32 || GEO >= 3 ? 2 : 1)))))
 void resblock3_kernel(ResBlock3Args a) {
   constexpr bool XB = (PL & kPlaneXB16) != 0, YB = (PL & kPlaneYB16) != 0;
   using PX = PlaneT<XB>;
   using PY = PlaneT<YB>;
   using P = Res3Cfg<S, C, GEO, K, NCV, XO, LEAD>;
+  using ROWS = typename P::ROWS;
   static_assert(NCV == 6 || NCV == 2, "ResBlock1 (6 convs) or ResBlock2 (2 convs)");
   constexpr int NP = S::NP;
   constexpr bool H3 = S::SCALED;
@@ -108,10 +124,14 @@ void resblock3_kernel(ResBlock3Args a) {
   const unsigned avoff = (unsigned)lane * 16u;
   const unsigned chb = (unsigned)T * PX::ES;
   const rsrc_t rx = make_rsrc(plane_at<XB>(a.x, (size_t)b * C * T), (unsigned)C * chb);
-  auto ldx = [&](unsigned off, auto pol_tag) -> float {
-    if constexpr (XB) return PX::ld(rx, off, 0u);
-    else return bload_x<decltype(pol_tag)::value>(rx, off, 0u);
+  auto ldx = [&](unsigned off, auto pol_tag, unsigned soff = 0u) -> float {
+    if constexpr (XB) return PX::ld(rx, off, soff);
+    else return bload_x<decltype(pol_tag)::value>(rx, off, soff);
   };
+  // GEO 4 (256 registers for a 64 x 64 wave tile) addresses the accumulator layout's 16 channels
+  // of a lane as one per-lane offset (column and the lane's half) plus a wave-uniform scalar
+  // offset per channel, instead of 16 per-lane offsets for each of the wave's TM x TN blocks
+  constexpr bool SOFF = GEO == 4;
 
   // ---- prologue: lrelu(x0) pieces for columns [-XO, RP_W + XO) of every 16-channel group, and x0
   // itself in the acc layout.  Every load is issued before the first store (one HBM latency for
@@ -155,11 +175,15 @@ void resblock3_kernel(ResBlock3Args a) {
         for (int n = 0; n < TN; ++n) {
           const int t = tx0 + xcol0 + n * 32;
           const bool tok = t >= 0 && t < T;
+          const unsigned vlane = tok ? (unsigned)(4 * half) * chb + (unsigned)t * PX::ES : OOB_OFF;
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int co = mrow0 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-            xr[m][n][r] = ldx(tok ? (unsigned)co * chb + (unsigned)t * PX::ES : OOB_OFF,
-                              std::integral_constant<int, R3_XR_POL>{});
+            if constexpr (SOFF)
+              xr[m][n][r] = ldx(vlane, std::integral_constant<int, R3_XR_POL>{}, (unsigned)(co - 4 * half) * chb);
+            else
+              xr[m][n][r] = ldx(tok ? (unsigned)co * chb + (unsigned)t * PX::ES : OOB_OFF,
+                                std::integral_constant<int, R3_XR_POL>{});
           }
         }
     };
@@ -177,7 +201,12 @@ void resblock3_kernel(ResBlock3Args a) {
             v[j] = lrelu2(xv[g][i][j], 0.1f);
             if (H3) v[j] *= xs;
           }
-          split_store4<S>(smem + (g * PR + r) * S::ROWB + 8 * quad_pos(q), v[0], v[1], v[2], v[3]);
+          // channel quad q sits at position 4 quad_pos(q): unit quad_pos(q) / 2, its low or high 8 bytes
+          const int qp = quad_pos(q);
+          unsigned char* dst[NP];
+#pragma unroll
+          for (int p = 0; p < NP; ++p) dst[p] = smem + ROWS::off(g * PR + r, (qp >> 1) + 2 * p) + 8 * (qp & 1);
+          split_store4<S>(dst, v[0], v[1], v[2], v[3]);
         }
       }
     __builtin_amdgcn_sched_barrier(0);  // keep the loads below the window's use
@@ -195,7 +224,11 @@ void resblock3_kernel(ResBlock3Args a) {
   f32x16 acc[TM][TN];
   f32x4 ar[PD + 1][TM][NP], bcur[TN][NP], bnext[TN][NP];
   rsrc_t ra[TM];
-  auto conv = [&](int wi, int roff, int kstep) {
+  auto conv = [&](int wi, int roff, int kstep) __attribute__((always_inline)) {
+    // swizzled rows: an operand address costs a few VALU per (g, k) and is no immediate offset.
+    // Keep the convs2 call (roff 0, kstep 1 in every iteration) from having its 48 addresses
+    // hoisted out of the iteration loop, where they would live across the whole kernel
+    if constexpr (ROWS::SWIZZLED) asm volatile("" : "+s"(roff), "+s"(kstep));
 #pragma unroll
     for (int m = 0; m < TM; ++m) ra[m] = make_rsrc(a.w[wi] + ((size_t)(wm * TM + m) * NC * K) * (NP * 256), 0xFFFFFFFFu);
 #pragma unroll
@@ -208,12 +241,14 @@ void resblock3_kernel(ResBlock3Args a) {
       for (int m = 0; m < TM; ++m)
 #pragma unroll
         for (int q = 0; q < NP; ++q) ar[p][m][q] = bload4(ra[m], avoff, (unsigned)(p * NP + q) * 1024u);
-    auto read_b = [&](int g, int k, f32x4 (*dst)[NP]) {
+    auto read_b = [&](int g, int k, f32x4 (*dst)[NP]) __attribute__((always_inline)) {
 #pragma unroll
       for (int n = 0; n < TN; ++n) {
-        const unsigned char* pp = smem + (g * PR + xcol0 + n * 32 + roff + k * kstep) * S::ROWB + 16 * half;
+        // 32 n rows further on: the same unit map (res3_layout.hpp), so one address per (g, k)
+        const int o = ROWS::off(g * PR + xcol0 + roff + k * kstep, half);
 #pragma unroll
-        for (int q = 0; q < NP; ++q) dst[n][q] = *reinterpret_cast<const f32x4*>(pp + 32 * q);
+        for (int q = 0; q < NP; ++q)
+          dst[n][q] = *reinterpret_cast<const f32x4*>(smem + ROWS::piece(o, q) + n * 32 * ROWS::PITCH);
       }
     };
     read_b(0, 0, bcur);
@@ -256,7 +291,7 @@ void resblock3_kernel(ResBlock3Args a) {
   // red halves alternate per call, and the store_pieces barrier between two calls separates a
   // half's reads from its next writes, so one barrier per call suffices
   int red_half = 0;
-  auto tile_exp = [&](float vmax) -> int {
+  auto tile_exp = [&](float vmax) __attribute__((always_inline)) -> int {
     if (!H3) return 0;
     vmax = wave_max(vmax);
     if (lane == 0) red[red_half][wave] = vmax;
@@ -276,25 +311,32 @@ void resblock3_kernel(ResBlock3Args a) {
 
   // acc-layout values (already zeroed where invalid) -> split pieces at LDS row column + roff;
   // rows of the region outside [roff, roff + RP_W) are zeroed
-  auto store_pieces = [&](int roff, float scale) {
+  auto store_pieces = [&](int roff, float scale) __attribute__((always_inline)) {
+    if constexpr (ROWS::SWIZZLED) asm volatile("" : "+s"(roff));  // as in conv: addresses formed here
 #pragma unroll
     for (int m = 0; m < TM; ++m)
 #pragma unroll
       for (int n = 0; n < TN; ++n)
 #pragma unroll
-        for (int gl = 0; gl < 2; ++gl)
-          store_xt8<S>(smem + (((mrow0 + m * 32) / 16 + gl) * PR + xcol0 + n * 32 + roff) * S::ROWB + 16 * half,
-                       acc[m][n], 8 * gl, scale);
-    // edge rows: [0, roff) and [roff + RP_W, PR) of every group
-    constexpr int EB = 2 * XO * S::ROWB;  // upper bound of edge bytes per group
+        for (int gl = 0; gl < 2; ++gl) {
+          const int o = ROWS::off(((mrow0 + m * 32) / 16 + gl) * PR + xcol0 + roff, half);
+          unsigned char* dst[NP];
+#pragma unroll
+          for (int p = 0; p < NP; ++p) dst[p] = smem + ROWS::piece(o, p) + n * 32 * ROWS::PITCH;
+          store_xt8<S>(dst, acc[m][n], 8 * gl, scale);
+        }
+    // edge rows: [0, roff) and [roff + RP_W, PR) of every group.  Whole rows are zeroed, so the
+    // order of the units inside a row (ROWS::unit) does not matter here, only the pitch
+    constexpr int ROWB = ROWS::PITCH;
+    constexpr int EB = 2 * XO * ROWB;  // upper bound of edge bytes per group
     for (int e = tid * 16; e < NC * EB; e += NT * 16) {
       const int g = e / EB;
       const int o = e - g * EB;  // byte in the edge area: first roff rows, then the tail
-      const int lead_b = roff * S::ROWB;
-      const int tail_b = (PR - roff - RP_W) * S::ROWB;
-      if (o < lead_b) *reinterpret_cast<f32x4*>(smem + g * PR * S::ROWB + o) = f32x4{};
+      const int lead_b = roff * ROWB;
+      const int tail_b = (PR - roff - RP_W) * ROWB;
+      if (o < lead_b) *reinterpret_cast<f32x4*>(smem + g * PR * ROWB + o) = f32x4{};
       else if (o - lead_b < tail_b)
-        *reinterpret_cast<f32x4*>(smem + (g * PR + roff + RP_W) * S::ROWB + (o - lead_b)) = f32x4{};
+        *reinterpret_cast<f32x4*>(smem + (g * PR + roff + RP_W) * ROWB + (o - lead_b)) = f32x4{};
     }
   };
 
@@ -302,7 +344,7 @@ void resblock3_kernel(ResBlock3Args a) {
   int lo = -XO, hi = RP_W + XO;  // valid columns of the staged operand
   // conv ci adds the residual: x = conv(.) + x; the next conv's operand lrelu(x) goes to the X
   // rows (column + XO)
-  auto residual_to_lds = [&](int ci) {
+  auto residual_to_lds = [&](int ci) __attribute__((always_inline)) {
     const float sc = H3 ? ldexpf(1.f, ex + a.w_exp[ci]) : 1.f;
     const float* bs = bsm + ci * C;
     float vmax = 0.f;
@@ -333,7 +375,7 @@ void resblock3_kernel(ResBlock3Args a) {
     ex = e2;
   };
   // the block's last conv: x_out = conv(.) + x -> MRF z (kept columns [LEAD, LEAD + RP_BN) only)
-  auto final_to_z = [&](int ci) {
+  auto final_to_z = [&](int ci) __attribute__((always_inline)) {
     const float sc = H3 ? ldexpf(1.f, ex + a.w_exp[ci]) : 1.f;
     const float* bs = bsm + ci * C;
     const unsigned chbz = (unsigned)T * PY::ES;
@@ -349,13 +391,19 @@ void resblock3_kernel(ResBlock3Args a) {
         const int col = xcol0 + n * 32;
         const int t = tx0 + col;
         const bool keep = col >= LEAD && col < LEAD + P::RP_BN && t >= 0 && t < T;
-        unsigned vo[16];
+        unsigned vo[16], so[16];
         float zv[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int co = mrow0 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-          vo[r] = keep ? (unsigned)co * chbz + (unsigned)t * PY::ES : OOB_OFF;
-          zv[r] = a.zmode >= 2 ? PY::ld(rz, vo[r], 0u) : 0.f;
+          if constexpr (SOFF) {
+            vo[r] = keep ? (unsigned)(4 * half) * chbz + (unsigned)t * PY::ES : OOB_OFF;
+            so[r] = (unsigned)(co - 4 * half) * chbz;
+          } else {
+            vo[r] = keep ? (unsigned)co * chbz + (unsigned)t * PY::ES : OOB_OFF;
+            so[r] = 0u;
+          }
+          zv[r] = a.zmode >= 2 ? PY::ld(rz, vo[r], so[r]) : 0.f;
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -363,7 +411,7 @@ void resblock3_kernel(ResBlock3Args a) {
           if (a.zmode == 2) v = zv[r] + v;
           else if (a.zmode == 3) v = (zv[r] + v) / a.zdiv;
           if (keep) vmax = fmaxf(vmax, fabsf(v));
-          PY::st(rz, v, vo[r], 0u);
+          PY::st(rz, v, vo[r], so[r]);
         }
       }
     }
@@ -371,8 +419,10 @@ void resblock3_kernel(ResBlock3Args a) {
   };
 
   if constexpr (NCV == 6) {
-#pragma unroll 1
-    for (int it = 0; it < 3; ++it) {
+    // one ResBlock1 iteration; LAST 0: the last one is told at run time (one loop body), 1 / 2:
+    // known not to be / to be the last
+    auto iteration = [&](int it, auto last_tag) __attribute__((always_inline)) {
+      constexpr int LAST = decltype(last_tag)::value;
       const int d = a.dil[it];
       // ---- convs1[it] on lrelu(x) (X rows = column + XO): taps at column + (k - HK) * d
       conv(2 * it, XO - HK * d, d);
@@ -411,8 +461,18 @@ void resblock3_kernel(ResBlock3Args a) {
       conv(2 * it + 1, 0, 1);
       lo += HK;
       hi -= HK;
-      if (it < 2) residual_to_lds(2 * it + 1);
+      if (LAST == 1 || (LAST == 0 && it < 2)) residual_to_lds(2 * it + 1);
       else final_to_z(2 * it + 1);
+    };
+    if constexpr (GEO == 4) {
+      // the 256-register form peels the last iteration: with the z epilogue inside the loop body
+      // the compiler carries the residual x in two register sets and spills one block of it
+#pragma unroll 1
+      for (int it = 0; it < 2; ++it) iteration(it, std::integral_constant<int, 1>{});
+      iteration(2, std::integral_constant<int, 2>{});
+    } else {
+#pragma unroll 1
+      for (int it = 0; it < 3; ++it) iteration(it, std::integral_constant<int, 0>{});
     }
   } else {
 #pragma unroll 1

@@ -109,6 +109,15 @@ __device__ __forceinline__ void split_store4(unsigned char* dst, float v0, float
 #pragma unroll
   for (int p = 0; p < S::NP; ++p) *reinterpret_cast<u32x2*>(dst + 32 * p) = u32x2{w0[p], w1[p]};
 }
+// the same with one destination per piece (row layouts that do not keep the pieces 32 bytes apart)
+template <class S>
+__device__ __forceinline__ void split_store4(unsigned char* const (&dst)[S::NP], float v0, float v1, float v2, float v3) {
+  unsigned w0[S::NP], w1[S::NP];
+  S::split2(v0, v1, w0);
+  S::split2(v2, v3, w1);
+#pragma unroll
+  for (int p = 0; p < S::NP; ++p) *reinterpret_cast<u32x2*>(dst[p]) = u32x2{w0[p], w1[p]};
+}
 
 // Accumulator registers r0 .. r0 + 7 of one lane (8 channels of one 16-channel group, positions
 // 8 half .. + 7 in quad_pos order) -> split pieces, one 16-byte store per piece at dst + 32 p
@@ -122,6 +131,16 @@ __device__ __forceinline__ void store_xt8(unsigned char* dst, const V& acc, int 
 #pragma unroll
   for (int p = 0; p < S::NP; ++p)
     *reinterpret_cast<u32x4_t*>(dst + 32 * p) = u32x4_t{w[0][p], w[1][p], w[2][p], w[3][p]};
+}
+// the same with one destination per piece
+template <class S, class V>
+__device__ __forceinline__ void store_xt8(unsigned char* const (&dst)[S::NP], const V& acc, int r0, float scale) {
+  unsigned w[4][S::NP];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) S::split2(acc[r0 + 2 * k] * scale, acc[r0 + 2 * k + 1] * scale, w[k]);
+#pragma unroll
+  for (int p = 0; p < S::NP; ++p)
+    *reinterpret_cast<u32x4_t*>(dst[p]) = u32x4_t{w[0][p], w[1][p], w[2][p], w[3][p]};
 }
 
 // Exponent e such that max|x| * 2^-e lies in [2^13, 2^14): read the 64 max-abs slots the
