@@ -839,6 +839,94 @@ int tts_forward_tts_decode_profiled(void* handle, const float* d_o_en, const flo
 int tts_forward_tts_block(void* handle, int decoder, const float* d_x, const int64_t* d_key_lengths, int B, int T,
                           float* d_y, void* hip_stream);
 
+/* ---- Tacotron2 (TTS/tts/models/tacotron2.py, inference; location-sensitive attention, "original"
+ * prenet) ----
+ * The decoder is a chain of dependent steps, each at most 5 launches on the caller's stream:
+ * attention RNN, attention, decoder RNN, projection, stop / bookkeeping / next prenet.  Steps are
+ * enqueued in chunks of `chunk`; after each chunk the host reads one word and stops when every
+ * utterance has ended.  math_mode TTS_MATH_BF16 stores the attention and decoder RNN matrices as
+ * bf16 (fp32 state, cell and accumulation) and runs the encoder / postnet convs in bf16; every other
+ * mode keeps fp32 weights with exact fp32 FMA products in the recurrent kernels and fp32x6 convs.
+ * Limits (TTS_ERR_UNSUPPORTED): B <= TTS_TACOTRON2_MAX_BATCH, T_en <= TTS_TACOTRON2_MAX_TOKENS,
+ * encoder_dim / 2 and query_dim multiples of TTS_LSTM_UNIT_BLOCK, attention_dim <= 128,
+ * location_filters <= 32, odd location_kernel_size <= 31, query_dim <= 2048, prenet_dim <= 1024,
+ * out_channels * r <= 1024. */
+#define TTS_TACOTRON2_MAX_BATCH 32
+#define TTS_TACOTRON2_MAX_TOKENS 2048
+#define TTS_LSTM_UNIT_BLOCK 4 /* hidden units (four gate rows each) one workgroup of the LSTM step owns */
+typedef struct TtsTacotron2Cfg {
+  int num_chars;
+  int out_channels; /* 80 */
+  int r;            /* reduction factor: frames per decoder step */
+  int encoder_dim, query_dim, prenet_dim, attention_dim; /* 512, 1024, 256, 128 */
+  int location_filters, location_kernel_size;           /* 32, 31 */
+  int attention_norm; /* 0: sigmoid(e) / sum sigmoid(e) (the config default), 1: softmax */
+  int embed_dim;      /* width appended to every encoder output (speaker embedding or d-vector); 0: none */
+  int num_speakers;   /* rows of speaker_embedding.weight [num_speakers][embed_dim]; 0: none (d-vectors) */
+  int chunk;          /* decoder steps enqueued between two host reads of the all-done word; 0: 32 */
+  int math_mode;
+} TtsTacotron2Cfg;
+
+/* Host weight order, E = encoder_dim, He = E / 2, Q = query_dim, P = prenet_dim, A = attention_dim,
+ * D = E + embed_dim, C = out_channels:
+ *   embedding.weight [num_chars][E];
+ *   encoder.convolutions.{0,1,2}: convolution1d.weight [E][E][5], .bias, batch_normalization.weight,
+ *     .bias, .running_mean, .running_var;
+ *   encoder.lstm: weight_ih_l0 [4He][E], weight_hh_l0 [4He][He], bias_ih_l0, bias_hh_l0, then the four
+ *     *_reverse;
+ *   decoder.prenet.linear_layers.{0,1}.linear_layer.weight [P][C], [P][P];
+ *   decoder.attention_rnn: weight_ih [4Q][P + D], weight_hh [4Q][Q], bias_ih, bias_hh;
+ *   decoder.attention: query_layer [A][Q], inputs_layer [A][D], v.weight [A], v.bias [1],
+ *     location_conv1d.weight [F][2][k], location_dense.weight [A][F];
+ *   decoder.decoder_rnn: weight_ih [4Q][Q + D], weight_hh [4Q][Q], bias_ih, bias_hh;
+ *   decoder.linear_projection: weight [C r][Q + D], bias; decoder.stopnet.1: weight [Q + C r], bias [1];
+ *   postnet.convolutions.{0..4}: as the encoder's (C -> 512 -> 512 -> 512 -> 512 -> C, kernel 5);
+ *   speaker_embedding.weight [num_speakers][embed_dim] (num_speakers > 0). */
+int tts_tacotron2_num_weights(const TtsTacotron2Cfg* cfg);
+int64_t tts_tacotron2_weight_numel(const TtsTacotron2Cfg* cfg, int index);
+int tts_tacotron2_create(const TtsTacotron2Cfg* cfg, const float* const* host_weights, int device, void** handle);
+int tts_tacotron2_destroy(void* handle);
+/* Embedding -> 3 x (conv k5, folded BatchNorm, ReLU) -> biLSTM (one launch per token, both directions),
+ * then the speaker vector appended and inputs_layer applied.  d_tokens [B][T_en] int64; d_x_lengths [B]
+ * int64 or NULL (every token valid, the reference): with lengths the biLSTM has pack_padded_sequence
+ * semantics (the reverse direction starts at each utterance's last token, padded outputs are 0).
+ * Token and speaker ids outside their tables read row 0 (no device-side error; the Python module checks
+ * them on the host and raises as torch's embedding does).
+ * d_speaker_ids [B] int64 (num_speakers > 0) or d_d_vectors [B][embed_dim] (num_speakers == 0 and
+ * embed_dim > 0); NULL otherwise.  Outputs: d_inputs [B][T_en][D], d_processed_inputs [B][A][T_en]. */
+int tts_tacotron2_encode(void* handle, const int64_t* d_tokens, const int64_t* d_x_lengths,
+                         const int64_t* d_speaker_ids, const float* d_d_vectors, int B, int T_en, float* d_inputs,
+                         float* d_processed_inputs, void* hip_stream);
+/* The step loop.  d_x_lengths [B] or NULL: attention keys at or past the length are masked.  Utterance b
+ * ends at its first step t >= 1 with stop > stop_threshold, or after max_decoder_steps; d_steps [B]
+ * int32 receives its step count.  d_decoder_outputs [B][max_decoder_steps][C r], d_alignments
+ * [B][max_decoder_steps][T_en] and d_stop_tokens [B][max_decoder_steps] are zeroed first and rows past
+ * an utterance's end stay zero (the caller sizes them for max_decoder_steps, whatever the utterances end up
+ * needing).  Synchronises the stream once per chunk; *steps_run (host, may be
+ * NULL) = the largest step count. */
+int tts_tacotron2_decode(void* handle, const float* d_inputs, const float* d_processed_inputs,
+                         const int64_t* d_x_lengths, int B, int T_en, int max_decoder_steps, float stop_threshold,
+                         float* d_decoder_outputs, float* d_alignments, float* d_stop_tokens, int32_t* d_steps,
+                         int* steps_run, void* hip_stream);
+int tts_tacotron2_decode_profiled(void* handle, const float* d_inputs, const float* d_processed_inputs,
+                                  const int64_t* d_x_lengths, int B, int T_en, int max_decoder_steps,
+                                  float stop_threshold, float* d_decoder_outputs, float* d_alignments,
+                                  float* d_stop_tokens, int32_t* d_steps, int* steps_run, void* hip_stream,
+                                  TtsLaunchRecord* records, int max_records, int* n_records);
+/* d_model_outputs [B][steps r][C] = decoder_outputs + postnet(decoder_outputs), rows at or past
+ * d_steps[b] * r zero; d_decoder_outputs [B][row_stride][C r] of which the first `steps` rows are
+ * read (row_stride = decode's max_decoder_steps).  Every utterance sees zero padding past its own end,
+ * as a batch of one does. */
+int tts_tacotron2_postnet(void* handle, const float* d_decoder_outputs, const int32_t* d_steps, int B, int steps,
+                          int row_stride, float* d_model_outputs, void* hip_stream);
+/* One LSTMCell step (gate order i, f, g, o), for kernel tests: d_x [B][I], d_h, d_c [B][H] and the
+ * outputs d_h_out, d_c_out [B][H] on the device, torch-layout weights on the host (w_ih [4H][I],
+ * w_hh [4H][H], b_ih, b_hh [4H]).  math_mode TTS_MATH_BF16: bf16 matrices; else fp32 FMA.
+ * B <= 32 and H % TTS_LSTM_UNIT_BLOCK == 0 (TTS_ERR_UNSUPPORTED otherwise).  Column b does not depend on B. */
+int tts_op_lstm_cell(const float* d_x, const float* d_h, const float* d_c, int B, int I, int H, const float* h_w_ih,
+                     const float* h_w_hh, const float* h_b_ih, const float* h_b_hh, int math_mode, float* d_h_out,
+                     float* d_c_out, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

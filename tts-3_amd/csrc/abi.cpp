@@ -15,6 +15,7 @@
 #include "mas.hpp"
 #include "melgan.hpp"
 #include "stft.hpp"
+#include "tacotron2.hpp"
 #include "text.hpp"
 #include "vits.hpp"
 #include "tts_mi355x.h"
@@ -946,6 +947,75 @@ int tts_forward_tts_block(void* handle, int decoder, const float* d_x, const int
     TTS_REQUIRE(handle, 1, "NULL handle");
     static_cast<tts::ForwardTts*>(handle)->block(decoder != 0, d_x, d_key_lengths, B, T, d_y,
                                                  static_cast<hipStream_t>(hip_stream));
+  });
+}
+
+// ----------------------------------------------------------------------------- Tacotron2
+int tts_tacotron2_num_weights(const TtsTacotron2Cfg* cfg) {
+  return num_weights(cfg, tts::tacotron2_validate, tts::tacotron2_weight_shapes);
+}
+
+int64_t tts_tacotron2_weight_numel(const TtsTacotron2Cfg* cfg, int idx) {
+  return weight_numel(cfg, idx, tts::tacotron2_validate, tts::tacotron2_weight_shapes);
+}
+
+int tts_tacotron2_create(const TtsTacotron2Cfg* cfg, const float* const* host_weights, int device, void** handle) {
+  return create<tts::Tacotron2>(cfg, host_weights, device, handle);
+}
+
+int tts_tacotron2_destroy(void* handle) { return destroy<tts::Tacotron2>(handle); }
+
+int tts_tacotron2_encode(void* handle, const int64_t* d_tokens, const int64_t* d_x_lengths,
+                         const int64_t* d_speaker_ids, const float* d_d_vectors, int B, int T_en, float* d_inputs,
+                         float* d_processed_inputs, void* hip_stream) {
+  return guarded([&] {
+    TTS_REQUIRE(handle, 1, "NULL handle");
+    static_cast<tts::Tacotron2*>(handle)->encode(d_tokens, d_x_lengths, d_speaker_ids, d_d_vectors, B, T_en, d_inputs,
+                                                 d_processed_inputs, static_cast<hipStream_t>(hip_stream));
+  });
+}
+
+int tts_tacotron2_decode(void* handle, const float* d_inputs, const float* d_processed_inputs,
+                         const int64_t* d_x_lengths, int B, int T_en, int max_decoder_steps, float stop_threshold,
+                         float* d_decoder_outputs, float* d_alignments, float* d_stop_tokens, int32_t* d_steps,
+                         int* steps_run, void* hip_stream) {
+  return guarded([&] {
+    TTS_REQUIRE(handle, 1, "NULL handle");
+    const int n = static_cast<tts::Tacotron2*>(handle)->decode(
+        d_inputs, d_processed_inputs, d_x_lengths, B, T_en, max_decoder_steps, stop_threshold, d_decoder_outputs,
+        d_alignments, d_stop_tokens, d_steps, static_cast<hipStream_t>(hip_stream));
+    if (steps_run) *steps_run = n;
+  });
+}
+
+int tts_tacotron2_decode_profiled(void* handle, const float* d_inputs, const float* d_processed_inputs,
+                                  const int64_t* d_x_lengths, int B, int T_en, int max_decoder_steps,
+                                  float stop_threshold, float* d_decoder_outputs, float* d_alignments,
+                                  float* d_stop_tokens, int32_t* d_steps, int* steps_run, void* hip_stream,
+                                  TtsLaunchRecord* records, int max_records, int* n_records) {
+  auto body = [&](tts::Tacotron2& h, hipStream_t s, tts::Profiler* prof) {
+    const int n = h.decode(d_inputs, d_processed_inputs, d_x_lengths, B, T_en, max_decoder_steps, stop_threshold,
+                           d_decoder_outputs, d_alignments, d_stop_tokens, d_steps, s, prof);
+    if (steps_run) *steps_run = n;
+  };
+  return profiled<tts::Tacotron2>(handle, hip_stream, records, max_records, n_records, body);
+}
+
+int tts_tacotron2_postnet(void* handle, const float* d_decoder_outputs, const int32_t* d_steps, int B, int steps,
+                          int row_stride, float* d_model_outputs, void* hip_stream) {
+  return guarded([&] {
+    TTS_REQUIRE(handle, 1, "NULL handle");
+    static_cast<tts::Tacotron2*>(handle)->postnet(d_decoder_outputs, d_steps, B, steps, row_stride, d_model_outputs,
+                                                  static_cast<hipStream_t>(hip_stream));
+  });
+}
+
+int tts_op_lstm_cell(const float* d_x, const float* d_h, const float* d_c, int B, int I, int H, const float* h_w_ih,
+                     const float* h_w_hh, const float* h_b_ih, const float* h_b_hh, int math_mode, float* d_h_out,
+                     float* d_c_out, void* hip_stream) {
+  return guarded([&] {
+    tts::op_lstm_cell(d_x, d_h, d_c, B, I, H, h_w_ih, h_w_hh, h_b_ih, h_b_hh, math_mode, d_h_out, d_c_out,
+                      static_cast<hipStream_t>(hip_stream));
   });
 }
 

@@ -8,6 +8,7 @@
 #include "common.hpp"
 #include "melgan.hpp"
 #include "stft.hpp"
+#include "tacotron2.hpp"
 #include "wino_consts.hpp"
 
 namespace tts {
@@ -312,6 +313,58 @@ void pack_melgan_block(int mode, const float* w1, const float* b1, const float* 
     bias1[r] = r < C ? b1[r] : 0.f;
     bias2[r] = r < C ? b2[r] + bs[r] : 0.f;
   }
+}
+
+// ---- skinny recurrent products (tacotron2.hpp): out[rb][k][j] = W[row(16 rb + j)][k], k < Kp ----
+int64_t packed_skinny_numel(int R, int K, bool bf16) {
+  const int64_t n = (int64_t)ceil_div(R, kSkinnyRows) * skinny_kp(K) * kSkinnyRows;
+  return bf16 ? n / 2 : n;
+}
+
+int64_t packed_lstm_numel(int H, int K, bool bf16) {
+  TTS_REQUIRE(H >= kLstmUnitBlock && H % kLstmUnitBlock == 0, 3,
+              "LSTM: the hidden size must be a multiple of " + std::to_string(kLstmUnitBlock));
+  return packed_skinny_numel(4 * H, K, bf16);
+}
+
+namespace {
+// entry(row, k): the value of packed row `row` (< 16 * blocks), column k (< K)
+template <class F>
+void pack_skinny(int blocks, int K, bool bf16, float* out, F&& entry) {
+  const int Kp = skinny_kp(K);
+  uint16_t* out16 = reinterpret_cast<uint16_t*>(out);
+  int64_t o = 0;
+  for (int rb = 0; rb < blocks; ++rb)
+    for (int k = 0; k < Kp; ++k)
+      for (int j = 0; j < kSkinnyRows; ++j, ++o) {
+        const float v = k < K ? entry(rb * kSkinnyRows + j, k) : 0.f;
+        if (bf16) out16[o] = f2bf_rne(v);
+        else out[o] = v;
+      }
+}
+}  // namespace
+
+void pack_lstm(const float* w_ih, const float* w_hh, int H, int I, bool bf16, float* out) {
+  TTS_REQUIRE(H >= kLstmUnitBlock && H % kLstmUnitBlock == 0, 3,
+              "LSTM: the hidden size must be a multiple of " + std::to_string(kLstmUnitBlock));
+  TTS_REQUIRE(I >= 0 && w_hh && (I == 0 || w_ih), 1, "LSTM: bad weights");
+  pack_skinny(H / kLstmUnitBlock, I + H, bf16, out, [&](int row, int k) {
+    const int unit = row / 4, g = row % 4;  // 16 ub + 4 u + g = 4 (4 ub + u) + g
+    const int64_t r = (int64_t)g * H + unit;
+    return k < I ? w_ih[r * I + k] : w_hh[r * H + (k - I)];
+  });
+}
+
+void pack_lstm_bias(const float* b_ih, const float* b_hh, int H, float* out) {
+  for (int unit = 0; unit < H; ++unit)
+    for (int g = 0; g < 4; ++g)
+      out[4 * unit + g] = (b_ih ? b_ih[g * H + unit] : 0.f) + (b_hh ? b_hh[g * H + unit] : 0.f);
+}
+
+void pack_skinny_rows(const float* w, int R, int K, bool bf16, float* out) {
+  TTS_REQUIRE(R >= 1 && K >= 1 && w, 1, "skinny product: bad weights");
+  pack_skinny(ceil_div(R, kSkinnyRows), K, bf16, out,
+              [&](int row, int k) { return row < R ? w[(int64_t)row * K + k] : 0.f; });
 }
 
 }  // namespace tts

@@ -242,6 +242,30 @@ class TtsForwardTtsCfg(Structure):
     ]
 
 
+TACOTRON2_MAX_BATCH = 32
+TACOTRON2_MAX_TOKENS = 2048
+LSTM_UNIT_BLOCK = 4
+
+
+class TtsTacotron2Cfg(Structure):
+    _fields_ = [
+        ("num_chars", c_int),
+        ("out_channels", c_int),
+        ("r", c_int),
+        ("encoder_dim", c_int),
+        ("query_dim", c_int),
+        ("prenet_dim", c_int),
+        ("attention_dim", c_int),
+        ("location_filters", c_int),
+        ("location_kernel_size", c_int),
+        ("attention_norm", c_int),
+        ("embed_dim", c_int),
+        ("num_speakers", c_int),
+        ("chunk", c_int),
+        ("math_mode", c_int),
+    ]
+
+
 class TtsLaunchRecord(Structure):
     _fields_ = [("name", c_char * 48), ("flops", c_double), ("bytes", c_double), ("ms", c_float)]
 
@@ -483,6 +507,29 @@ SIGNATURES = {
          c_void_p, POINTER(TtsLaunchRecord), c_int, POINTER(c_int)],
     ),
     "tts_forward_tts_block": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "tts_tacotron2_num_weights": (c_int, [POINTER(TtsTacotron2Cfg)]),
+    "tts_tacotron2_weight_numel": (c_int64, [POINTER(TtsTacotron2Cfg), c_int]),
+    "tts_tacotron2_create": (c_int, [POINTER(TtsTacotron2Cfg), POINTER(c_void_p), c_int, POINTER(c_void_p)]),
+    "tts_tacotron2_destroy": (c_int, [c_void_p]),
+    "tts_tacotron2_encode": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    ),
+    "tts_tacotron2_decode": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
+         c_void_p, POINTER(c_int), c_void_p],
+    ),
+    "tts_tacotron2_decode_profiled": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
+         c_void_p, POINTER(c_int), c_void_p, POINTER(TtsLaunchRecord), c_int, POINTER(c_int)],
+    ),
+    "tts_tacotron2_postnet": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "tts_op_lstm_cell": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+         c_void_p, c_void_p],
+    ),
 }
 
 _lib = None

@@ -139,6 +139,40 @@ FAST_PITCH: Dict[str, Any] = {
     "use_d_vector_file": False,
 }
 
+# Tacotron2Config defaults the model reads (TTS/tts/configs/tacotron2_config.py) and the widths the
+# reference hard-codes in TTS/tts/models/tacotron2.py / layers/tacotron/tacotron2.py
+TACOTRON2: Dict[str, Any] = {
+    "num_chars": None,
+    "out_channels": 80,
+    "r": 2,
+    "attention_type": "original",
+    "attention_norm": "sigmoid",
+    "location_attn": True,
+    "windowing": False,
+    "use_forward_attn": False,
+    "transition_agent": False,
+    "forward_attn_mask": False,
+    "prenet_type": "original",
+    "prenet_dropout": True,
+    "prenet_dropout_at_inference": False,
+    "separate_stopnet": True,
+    "stop_threshold": 0.5,
+    "max_decoder_steps": 10000,
+    "num_speakers": 1,
+    "use_speaker_embedding": False,
+    "use_d_vector_file": False,
+    "d_vector_dim": 0,
+    "double_decoder_consistency": False,
+    "use_gst": False,
+    "use_capacitron_vae": False,
+    "encoder_dim": 512,
+    "query_dim": 1024,
+    "prenet_dim": 256,
+    "attention_dim": 128,
+    "location_filters": 32,
+    "location_kernel_size": 31,
+}
+
 
 def load_config(path: str) -> Dict[str, Any]:
     """Read a Coqui JSON config (``TTS/config/__init__.py:68-100`` reads the same files)."""

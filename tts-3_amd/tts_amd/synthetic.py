@@ -685,6 +685,86 @@ def forward_tts_state_dict(args, seed: int = 2024, attn_scale: float = 1.6) -> "
     return sd
 
 
+def tacotron2_state_dict(args, seed: int = 2024) -> "OrderedDict[str, torch.Tensor]":
+    """State dict of ``Tacotron2`` (``args``: a ``Tacotron2Args`` or a dict with its fields) with the
+    reference's keys.  Scales (std of the normal draws; fan = input width x kernel):
+    convs sqrt(2) / sqrt(fan) in the encoder (ReLU) and 1 / sqrt(fan) in the postnet, BatchNorm gain
+    1 + 0.1 N, bias and running mean 0.1 N, running variance in [0.5, 1.5]; LSTM and LSTMCell input matrices
+    1 / sqrt(fan), recurrent matrices 0.7 / sqrt(H) (a contracting recurrence: at 1.5 the free run is
+    chaotic and torch's own fp32 evaluation leaves the fp32 gates), biases 0.1 N; prenet sqrt(2) /
+    sqrt(fan); query / inputs / location-dense layers 2 / sqrt(fan), location conv 4 / sqrt(fan); the v
+    layer follows ``attention_norm``: 3 / sqrt(A) for softmax, 10 / sqrt(A) with bias -4 for sigmoid
+    (sigmoid(e) / sum only gives small weights for energies well below 0); projection 1.5 / sqrt(fan),
+    bias 0.1 N; stopnet 12 / sqrt(fan), bias 0.  Measured on the test inputs (tests/_tacotron2_cases.py)
+    over 40 free-running steps of the fp64 oracle, after the first three steps: alignment entropy 0.52 to
+    0.98 of log(length) (sigmoid, speaker embedding), 0.60 to 0.98 (softmax), 0.32 to 0.97 (d-vectors), the
+    largest weight 0.42 / 0.57 / 0.76; stop probabilities 0.33 to 0.95 (tests/test_tacotron2_cpu.py holds
+    these conditions, so a change of seed or scale fails there)."""
+    a = args if isinstance(args, dict) else vars(args)
+    g = lambda k, d: a.get(k, d)  # noqa: E731
+    E, Q, P, A = g("encoder_dim", 512), g("query_dim", 1024), g("prenet_dim", 256), g("attention_dim", 128)
+    Fl, Kl, C, r = g("location_filters", 32), g("location_kernel_size", 31), a["out_channels"], a["r"]
+    W = g("speaker_embedding_dim", 512) if g("use_speaker_embedding", False) else \
+        (g("d_vector_dim", 0) if g("use_d_vector_file", False) else 0)
+    D = E + W
+    rng = np.random.default_rng(seed)
+    sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+
+    def t(v):
+        return torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32))
+
+    def lin(name, out, inp, scale, bias=None):
+        sd[name + ".weight"] = t(rng.standard_normal((out, inp)) * (scale / np.sqrt(inp)))
+        if bias is not None:
+            sd[name + ".bias"] = t(rng.standard_normal(out) * bias)
+
+    def conv_bn(pre, cout, cin, scale):
+        sd[pre + "convolution1d.weight"] = t(rng.standard_normal((cout, cin, 5)) * (scale / np.sqrt(cin * 5)))
+        sd[pre + "convolution1d.bias"] = t(rng.standard_normal(cout) * 0.02)
+        bn = pre + "batch_normalization."
+        sd[bn + "weight"] = t(1.0 + 0.1 * rng.standard_normal(cout))
+        sd[bn + "bias"] = t(0.1 * rng.standard_normal(cout))
+        sd[bn + "running_mean"] = t(0.1 * rng.standard_normal(cout))
+        sd[bn + "running_var"] = t(0.5 + rng.random(cout))
+        sd[bn + "num_batches_tracked"] = torch.tensor(1000, dtype=torch.int64)
+
+    def rnn(pre, H, I, sfx=""):
+        sd[f"{pre}weight_ih{sfx}"] = t(rng.standard_normal((4 * H, I)) * (1.0 / np.sqrt(I)))
+        sd[f"{pre}weight_hh{sfx}"] = t(rng.standard_normal((4 * H, H)) * (0.7 / np.sqrt(H)))
+        sd[f"{pre}bias_ih{sfx}"] = t(rng.standard_normal(4 * H) * 0.1)
+        sd[f"{pre}bias_hh{sfx}"] = t(rng.standard_normal(4 * H) * 0.1)
+
+    emb = rng.standard_normal((a["num_chars"], E))
+    emb[0] = 0.0  # padding_idx
+    sd["embedding.weight"] = t(emb)
+    for i in range(3):
+        conv_bn(f"encoder.convolutions.{i}.", E, E, np.sqrt(2.0))
+    rnn("encoder.lstm.", E // 2, E, "_l0")
+    rnn("encoder.lstm.", E // 2, E, "_l0_reverse")
+    lin("decoder.prenet.linear_layers.0.linear_layer", P, C, np.sqrt(2.0))
+    lin("decoder.prenet.linear_layers.1.linear_layer", P, P, np.sqrt(2.0))
+    rnn("decoder.attention_rnn.", Q, P + D)
+    lin("decoder.attention.query_layer.linear_layer", A, Q, 2.0)
+    lin("decoder.attention.inputs_layer.linear_layer", A, D, 2.0)
+    if g("attention_norm", "sigmoid") == "softmax":
+        lin("decoder.attention.v.linear_layer", 1, A, 3.0, bias=0.1)
+    else:  # sigmoid(e) / sum: only energies well below 0 give small weights
+        lin("decoder.attention.v.linear_layer", 1, A, 10.0, bias=0.1)
+        sd["decoder.attention.v.linear_layer.bias"] -= 4.0
+    sd["decoder.attention.location_layer.location_conv1d.weight"] = t(
+        rng.standard_normal((Fl, 2, Kl)) * (4.0 / np.sqrt(2 * Kl)))
+    lin("decoder.attention.location_layer.location_dense.linear_layer", A, Fl, 2.0)
+    rnn("decoder.decoder_rnn.", Q, Q + D)
+    lin("decoder.linear_projection.linear_layer", C * r, Q + D, 1.5, bias=0.1)
+    lin("decoder.stopnet.1.linear_layer", 1, Q + C * r, 12.0, bias=0.0)
+    dims = [C, 512, 512, 512, 512, C]
+    for i in range(5):
+        conv_bn(f"postnet.convolutions.{i}.", dims[i + 1], dims[i], 1.0)
+    if g("use_speaker_embedding", False):
+        sd["speaker_embedding.weight"] = t(rng.standard_normal((a["num_speakers"], W)) * 0.3)
+    return sd
+
+
 def tokens(batch: int, length: int, num_chars: int, seed: int = 0) -> torch.Tensor:
     """Synthetic token ids [B, T] uniform in [0, num_chars) (int64, CPU)."""
     g = torch.Generator().manual_seed(seed)
