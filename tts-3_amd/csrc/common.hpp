@@ -135,8 +135,23 @@ struct ResBlock3Args {
   unsigned* amax_out;       // [B][64] statistics of the stored value, or nullptr
   int T;
   int planes;               // 0, or kPlaneXB16 | kPlaneYB16: x and z are bf16 planes (MATH_BF16)
+  // up_w != nullptr (resblock3_up_supported): the block is the stage's last MRF launch and the
+  // next stage's x2 ConvTranspose1d runs on its result as a seventh conv.  The block's value takes
+  // branch 0's place in v = ((x + zp[0]) + zp[1]) / zdiv over the nzp other branches' planes
+  // (nzp = 0: v = x), which is not stored; up_y[b][C / 2][2 T] = ups(lrelu(v, 0.1)) is, with its
+  // statistics in up_amax.  z, zmode and amax_out are unused.
+  const float* up_w;        // the upsampler as the K = 2 conv of Conv1dArgs::ups (C rows, C channels)
+  const float* up_bias;     // [C], the bias repeated per phase
+  int up_w_exp;
+  float* up_y;
+  unsigned* up_amax;
+  const float* zp[2];       // [B][C][T] each
+  int nzp;
 };
 bool resblock3_supported(int mode, int C, int K, const int* dil);
+// the upsampling tail (ResBlock3Args::up_w): f16x3, kernel 3 at 64 / 128 channels, and a valid
+// column to spare on either side of the kept ones (the tail's K = 2 taps read z one column back)
+bool resblock3_up_supported(int mode, int C, int K, const int* dil);
 void launch_resblock3(int mode, const ResBlock3Args& a, int B, int C, int K, hipStream_t s);
 // A whole ResBlock2 (hifigan_generator.py:150-155: two convs of kernel K, dilations dil[0..1],
 // each x = conv(lrelu(x)) + x) in one kernel; ResBlock3Args with w / bias / w_exp[0..1].

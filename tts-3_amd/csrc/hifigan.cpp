@@ -233,6 +233,23 @@ Hifigan::Hifigan(const TtsHifiganCfg& cfg, const float* const* hw, int device)
       res_.push_back(rb);
     }
   }
+  // x2 upsamplers folded into the previous stage's kernel-3 whole block (hifigan.hpp ups_fused_):
+  // the block reads the upsampler's packing as it reads its own convs' ([32-row block][16-channel
+  // group][tap]), so the same conditions on the tile hold
+  ups_fused_.assign(cfg_.num_upsamples, 0);
+  const char* uf = std::getenv("TTS_MI355X_UPS_FUSION");
+  if (!(uf && uf[0] == '0') && cfg_.resblock_type == 1 && cfg_.num_kernels <= 3 && !cfg_.cond_in_each_up_layer &&
+      !planes16_) {
+    for (int i = 0; i + 1 < cfg_.num_upsamples; ++i) {
+      const int ch = C0 >> (i + 1);
+      const ConvTLayer& u = ups_[i + 1];
+      if (!res_[i * cfg_.num_kernels].fused3 || u.U != 2 || !is_split_mode(u.mode)) continue;
+      const ConvTile t = conv_tile(u.mode, u.tile);
+      const bool tile_ok = !t.WINO && t.CK % 16 == 0 && ch % t.CK == 0 && ch % t.BM == 0;
+      ups_fused_[i] = tile_ok && resblock3_up_supported(mode, ch, cfg_.resblock_kernel_sizes[0],
+                                                        cfg_.resblock_dilation_sizes[0]);
+    }
+  }
   const float* post_w = hw[wi]; wi += 1;
   post_bias_ = cfg_.conv_post_bias ? hw[wi][0] : 0.f;
   if (cfg_.conv_post_bias) wi += 1;
@@ -536,6 +553,10 @@ void Hifigan::forward_plain(const float* mel, int B, int C, int T, int pad, cons
   const int64_t plane = plane_floats(B, T, pad);
   float* bufZ = ws;               // conv_pre output, then the MRF sum of each stage
   float* bufO = ws + plane;       // upsampled stage input o
+  // the T plane of stream 0.  A stage whose block applies the next upsampler (ups_fused_) writes the
+  // next stage's input there, and the two planes swap roles: O is still being read by the block's
+  // other workgroups, and T is free once stream 0's branches are done
+  float* bufT0 = ws + 3 * plane;
   const int np = n_planes(lane ? lane->nbs : 1);  // the planes this schedule uses (lane_bytes)
   float* cvec = cfg_.cond_channels > 0 ? ws + np * plane : nullptr;
   const bool h3 = cfg_.math_mode == MATH_FP32_F16X3;
@@ -600,7 +621,11 @@ void Hifigan::forward_plain(const float* mel, int B, int C, int T, int pad, cons
     const double uflops = 2.0 * B * U.Cout * (double)U.Cin * 2 * lout;
     const double es = planes16_ ? 2.0 : 4.0;
     const double ubytes = es * ((double)B * U.Cin * len + (double)B * U.Cout * lout) + 4.0 * U.Cin * U.Cout * 2 * U.U;
-    if (is_split_mode(U.mode)) {
+    const bool fuse = ups_fused_[i] != 0;                 // this stage's block applies ups_[i + 1]
+    const bool ups_done = i > 0 && ups_fused_[i - 1] != 0;  // the previous stage's block wrote o
+    if (ups_done) {
+      // bufO already holds ups_[i](lrelu(z)) and slots(g0) its statistics
+    } else if (is_split_mode(U.mode)) {
       Conv1dArgs a{};
       a.planes = planes16_ ? kPlaneXB16 | kPlaneYB16 : 0;
       a.x = cur; a.w = U.w; a.bias = U.b; a.y = bufO;
@@ -620,33 +645,69 @@ void Hifigan::forward_plain(const float* mel, int B, int C, int T, int pad, cons
     len = lout;
     if (conc) TTS_HIP_CHECK(hipEventRecord(lane->ev_ups, s));  // o is ready for every branch
     // MRF: z = sum_j resblock_j(o); o = z / num_kernels (:255-261)
-    for (int j = 0; j < K; ++j) {
+    // A stage whose block applies the next upsampler (fuse) runs branches 1 .. K - 1 first, each
+    // leaving its result x in a plane of its own (zmode 0; no sum to keep in order), and the block,
+    // branch 0, last: it forms ((r0 + r1) + r2) / K from its registers and those planes, the same
+    // operations in the same association as the z plane's three writers
+    float* rplane[TTS_MAX_KERNELS] = {};
+    for (int jj = 0; jj < K; ++jj) {
+      const int j = fuse ? (jj + 1) % K : jj;
       const ResBlock& rb = res_[i * K + j];
       // branch j: its stream and that stream's X / T planes
       const int bj = conc ? bstream(j) : 0;
       const hipStream_t sj = bj > 0 ? lane->branch[bj - 1] : s;
       float* bufX = ws + (2 + 2 * bj) * plane;  // resblock running residual x
-      float* bufT = bufX + plane;               // convs1 output (already leaky-relu'd)
+      float* bufT = bj == 0 ? bufT0 : bufX + plane;  // convs1 output (already leaky-relu'd)
       if (bj > 0) TTS_HIP_CHECK(hipStreamWaitEvent(sj, lane->ev_ups, 0));
+      // fuse: where branch j's result stays until the block reads it.  Its stream's X plane, or Z
+      // (idle in such a stage: no sum is written) when a later branch takes the same stream's planes
+      float* const xres = (fuse && j + 1 < K && (conc ? bstream(j + 1) : 0) == bj) ? bufZ : bufX;
+      rplane[j] = xres;
       // the MRF-sum writer of branch j reads the z branch j - 1 wrote: keep that order
       auto zorder = [&] {
-        if (bj > 0 && bstream(j - 1) != bj) TTS_HIP_CHECK(hipStreamWaitEvent(sj, lane->ev_z[j - 1], 0));
+        if (!fuse && bj > 0 && bstream(j - 1) != bj) TTS_HIP_CHECK(hipStreamWaitEvent(sj, lane->ev_z[j - 1], 0));
       };
       auto zdone = [&] {
         if (conc) TTS_HIP_CHECK(hipEventRecord(lane->ev_z[j], sj));
       };
-      const int zlast = (cfg_.num_kernels == 1 || j == 0) ? 1 : (j == cfg_.num_kernels - 1 ? 3 : 2);
+      const int zlast = fuse ? 0 : ((cfg_.num_kernels == 1 || j == 0) ? 1 : (j == cfg_.num_kernels - 1 ? 3 : 2));
       const int gj = g0 + 1 + j * 6;  // slot group of conv c of this resblock: gj + c
       const int gz = g0 + 1 + cfg_.num_kernels * 6;  // the stage's z / num_kernels
-      if (cfg_.resblock_type == 1 && rb.fused3) {
+      if (fuse && j == 0) {
+        // the three iterations, the MRF mean and ups_[i + 1] in one launch: o -> the next stage's o
+        const ConvTLayer& Un = ups_[i + 1];
+        ResBlock3Args ra{};
+        ra.x = bufO; ra.amax_in = slots(g0);
+        for (int c = 0; c < 6; ++c) { ra.w[c] = rb.convs[c].w; ra.bias[c] = rb.convs[c].b; ra.w_exp[c] = rb.convs[c].w_exp; }
+        for (int m = 0; m < 3; ++m) ra.dil[m] = rb.convs[2 * m].dil;
+        ra.zdiv = (float)K;
+        ra.T = len;
+        ra.nzp = K - 1;
+        for (int p = 1; p < K; ++p) {
+          ra.zp[p - 1] = rplane[p];
+          // the block runs on s: the branches of other streams are done before it reads their planes
+          if (conc && bstream(p) > 0) TTS_HIP_CHECK(hipStreamWaitEvent(s, lane->ev_z[p], 0));
+        }
+        ra.up_w = Un.w; ra.up_bias = Un.b; ra.up_w_exp = Un.w_exp;
+        ra.up_y = bufT0; ra.up_amax = slots(stage_group(i + 1));
+        const ConvLayer& L1 = rb.convs[0];
+        const double flops = 12.0 * B * L1.Cout * (double)L1.Cin * L1.K * len +
+                             2.0 * B * Un.Cout * (double)Un.Cin * 2 * (2.0 * len);
+        // x and the other branches' planes read, the next stage's input (as large) written
+        const double bytes = 4.0 * B * L1.Cout * (double)len * (K + 1) + 4.0 * 6.0 * L1.Cout * L1.Cin * L1.K +
+                             4.0 * Un.Cin * Un.Cout * 2 * Un.U;
+        const std::string nm = "mrf_block_k" + std::to_string(L1.K) + "_c" + std::to_string(L1.Cout);
+        run(prof, s, nm.c_str(), flops, bytes, [&] { launch_resblock3(L1.mode, ra, B, L1.Cout, L1.K, s); });
+        std::swap(bufO, bufT0);  // the next stage reads what was T; the old O is its stream-0 T
+      } else if (cfg_.resblock_type == 1 && rb.fused3) {
         // the three iterations in one launch: o -> MRF z
         ResBlock3Args ra{};
         ra.x = bufO; ra.amax_in = slots(g0);
         ra.planes = planes16_ ? kPlaneXB16 | kPlaneYB16 : 0;
         for (int c = 0; c < 6; ++c) { ra.w[c] = rb.convs[c].w; ra.bias[c] = rb.convs[c].b; ra.w_exp[c] = rb.convs[c].w_exp; }
         for (int m = 0; m < 3; ++m) ra.dil[m] = rb.convs[2 * m].dil;
-        ra.z = bufZ; ra.zmode = zlast; ra.zdiv = (float)cfg_.num_kernels;
-        ra.amax_out = j == cfg_.num_kernels - 1 ? slots(gz) : nullptr;
+        ra.z = fuse ? xres : bufZ; ra.zmode = fuse ? 1 : zlast; ra.zdiv = (float)cfg_.num_kernels;
+        ra.amax_out = !fuse && j == cfg_.num_kernels - 1 ? slots(gz) : nullptr;
         ra.T = len;
         const ConvLayer& L1 = rb.convs[0];
         const double flops = 12.0 * B * L1.Cout * (double)L1.Cin * L1.K * len;
@@ -663,8 +724,8 @@ void Hifigan::forward_plain(const float* mel, int B, int C, int T, int pad, cons
           const ConvLayer& L1 = rb.convs[2 * m];
           const ConvLayer& L2 = rb.convs[2 * m + 1];
           const float* xin = (m == 0) ? bufO : (m == 1 ? bufX : bufT);
-          float* xout = (m == 1) ? bufT : bufX;
           const bool last = (m == 2);
+          float* xout = (m == 1) ? bufT : (last ? xres : bufX);
           ResPairArgs pa{};
           Conv1dArgs& c1 = pa.c1;
           c1.x = xin; c1.w = L1.w; c1.bias = L1.b; c1.Cin = L1.Cin; c1.Cout = L1.Cout; c1.Tin = len; c1.Tout = len;
@@ -678,7 +739,7 @@ void Hifigan::forward_plain(const float* mel, int B, int C, int T, int pad, cons
           c2.n_chunks = L2.n_chunks; c2.in_slope = 1.f; c2.out_slope = 1.f; c2.zmode = last ? zlast : 0;
           c2.zdiv = (float)cfg_.num_kernels; c2.w_exp = L2.w_exp;
           c2.planes = c1.planes;
-          c2.amax_out = last ? (j == cfg_.num_kernels - 1 ? slots(gz) : nullptr) : slots(gj + 2 * m + 1);
+          c2.amax_out = last ? (!fuse && j == cfg_.num_kernels - 1 ? slots(gz) : nullptr) : slots(gj + 2 * m + 1);
           // the generator's last MRF writer: conv_post runs in its epilogue (the final z never
           // reaches HBM); TTS_MI355X_POST_FUSION=0 keeps the separate conv_post launch
           const bool post = last && zlast == 3 && i == cfg_.num_upsamples - 1 && post_fusion_ &&
@@ -711,8 +772,8 @@ void Hifigan::forward_plain(const float* mel, int B, int C, int T, int pad, cons
                sj);
           // x = convs2[m](xt) + x                          (:97-98)
           if (last) zorder();
-          conv(rb.convs[2 * m + 1], bufT, len, len, 0, 1.f, 1.f, xin, bufX, last ? zlast : 0, nullptr,
-               slots(gj + 2 * m), last ? (j == cfg_.num_kernels - 1 ? slots(gz) : nullptr) : slots(gj + 2 * m + 1), sj);
+          conv(rb.convs[2 * m + 1], bufT, len, len, 0, 1.f, 1.f, xin, last ? xres : bufX, last ? zlast : 0, nullptr,
+               slots(gj + 2 * m), last ? (!fuse && j == cfg_.num_kernels - 1 ? slots(gz) : nullptr) : slots(gj + 2 * m + 1), sj);
           if (last) zdone();
         }
       } else if (rb.fused2) {
@@ -750,7 +811,8 @@ void Hifigan::forward_plain(const float* mel, int B, int C, int T, int pad, cons
       }
     }
     // the stage's z (and every branch before it) is complete before the next stage's ups
-    if (conc && bstream(K - 1) > 0) TTS_HIP_CHECK(hipStreamWaitEvent(s, lane->ev_z[K - 1], 0));
+    // (a fused stage's block, on s, has waited for them already)
+    if (!fuse && conc && bstream(K - 1) > 0) TTS_HIP_CHECK(hipStreamWaitEvent(s, lane->ev_z[K - 1], 0));
     cur = bufZ;
   }
   // leaky_relu (default slope 0.01!) -> conv_post -> tanh (:262-264)

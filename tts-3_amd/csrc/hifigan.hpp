@@ -121,6 +121,12 @@ class Hifigan {
   // MATH_BF16: the Z / O / X / T activation planes hold bf16 (conv_device.hpp PlaneT), halving the
   // bytes every kernel stages, gathers and stores; TTS_MI355X_BF16_PLANES=0 keeps fp32 planes
   bool planes16_ = false;
+  // ups_fused_[i]: stage i's kernel-3 whole block (branch 0) runs last in its stage, forms the MRF
+  // mean from its own result and the other branches' planes, and applies the x2 upsampler of
+  // stage i + 1 to it (ResBlock3Args::up_w): the mean never reaches HBM and stage i + 1 launches
+  // no upsampler.  f16x3, ResBlock1, at most three kernels, fp32 planes, no per-stage conditioning;
+  // TTS_MI355X_UPS_FUSION=0 keeps the separate launches
+  std::vector<char> ups_fused_;
   // defaults (A/B on MI355X, config 2): two sub-batch lanes with one stream each when B >= 2
   // (51.5 ms per batch), else one lane with a stream per MRF branch (51.8 ms at B = 32; 3 x 2
   // streams: 52.5 ms)

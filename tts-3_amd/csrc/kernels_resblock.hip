@@ -579,6 +579,15 @@ void launch_res3_t(const ResBlock3Args& a, int B, hipStream_t s) {
   dim3 grid(ceil_div(a.T, P::RP_BN), 1, B);
   launch_block_pl<S, C, GEO, K, 6, r3_xoff(K), r3_lead(K)>(a, grid, P::NT, s);
 }
+// the block with the upsampling tail (ResBlock3Args::up_w): the tiles, stride and lead of the plain
+// kernel-3 form (GEO 4 at 128 channels, GEO 2 at 64); column T, the x2 layer's last, goes to the
+// last workgroup
+template <class S, int C, int GEO>
+void launch_res3_up_t(const ResBlock3Args& a, int B, hipStream_t s) {
+  using P = Res3Cfg<S, C, GEO, 3, 6, r3_xoff(3), r3_lead(3), true>;
+  dim3 grid(ceil_div(a.T, P::RP_BN), 1, B);
+  hipLaunchKernelGGL((resblock3_kernel<S, C, GEO, 3, 6, r3_xoff(3), r3_lead(3), 0, true>), grid, dim3(P::NT), 0, s, a);
+}
 template <class S>
 void launch_res3_s(const ResBlock3Args& a, int B, int C, int K, hipStream_t s) {
   // C = 64: 128 columns (2 waves/SIMD, a quarter of the columns are halo; 192 columns at one
@@ -629,10 +638,34 @@ bool resblock3_supported(int mode, int C, int K, const int* dil) {
   return lo <= r3_lead(K);
 }
 
+bool resblock3_up_supported(int mode, int C, int K, const int* dil) {
+  if (mode != MATH_FP32_F16X3 || K != 3 || !(C == 64 || C == 128) || !resblock3_supported(mode, C, K, dil)) return false;
+  // the valid-range walk again, from both grid edges: output column c of the tail reads z at
+  // c - 1 and c, and the last workgroup also emits the column after its kept ones
+  const int rp_w = 128;
+  int lo = -r3_xoff(K), hi = rp_w + r3_xoff(K);
+  for (int m = 0; m < 3; ++m) {
+    lo = std::max(lo + dil[m], 0) + 1;
+    hi = std::min(hi - dil[m], rp_w) - 1;
+  }
+  return lo <= r3_lead(K) - 1 && hi >= rp_w - r3_lead(K) + 1;
+}
+
 void launch_resblock3(int mode, const ResBlock3Args& a, int B, int C, int K, hipStream_t s) {
   TTS_REQUIRE(resblock3_supported(mode, C, K, a.dil), 3, "resblock3: unsupported configuration");
-  TTS_REQUIRE(a.zmode >= 1 && a.zmode <= 3 && a.z && a.x && a.x != a.z, 1, "resblock3: bad arguments");
   TTS_REQUIRE((int64_t)C * a.T * 4 < (int64_t(1) << 31), 3, "resblock3: plane exceeds 2 GiB");
+  if (a.up_w) {
+    TTS_REQUIRE(resblock3_up_supported(mode, C, K, a.dil), 3, "resblock3: no upsampling tail for this configuration");
+    TTS_REQUIRE(a.x && a.up_y && a.up_y != a.x && a.up_bias && a.planes == 0 && a.nzp >= 0 && a.nzp <= 2, 1,
+                "resblock3: bad arguments of the upsampling tail");
+    for (int p = 0; p < a.nzp; ++p)
+      TTS_REQUIRE(a.zp[p] && a.zp[p] != a.up_y, 1, "resblock3: a branch plane is missing or aliases the tail's output");
+    if (C == 128) launch_res3_up_t<SchemeH3, 128, 4>(a, B, s);
+    else launch_res3_up_t<SchemeH3, 64, 2>(a, B, s);
+    TTS_HIP_CHECK(hipGetLastError());
+    return;
+  }
+  TTS_REQUIRE(a.zmode >= 1 && a.zmode <= 3 && a.z && a.x && a.x != a.z, 1, "resblock3: bad arguments");
   if (mode == MATH_FP32_F16X3) launch_res3_s<SchemeH3>(a, B, C, K, s);
   else if (mode == MATH_BF16) launch_res3_s<SchemeB1>(a, B, C, K, s);
   else launch_res3_s<SchemeX6>(a, B, C, K, s);

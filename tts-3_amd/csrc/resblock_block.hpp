@@ -57,7 +57,8 @@ constexpr int rb2_halo(int K) { return K == 3 ? 4 : (K == 5 ? 12 : (K == 7 ? 9 :
 // Measured (f16x3, per batch): C = 128 GEO 4 4.28 ms vs GEO 3 4.73 ms, bitwise the same output
 // (profiles/ab_block_c128_2wg.txt; earlier, GEO 3 5.0 ms vs GEO 2 5.5 ms); 8-wave forms at C = 64
 // (256 columns) and C = 32 (512 columns) were slower than GEO 2 / GEO 0 (+0.2 / +0.3 ms).
-template <class S, int C, int GEO, int K = 3, int NCV = 6, int XO = R3_XOFF, int LEAD = R3_LEAD>
+// UP: the upsampling tail (ResBlock3Args::up_w), one more bias row in LDS
+template <class S, int C, int GEO, int K = 3, int NCV = 6, int XO = R3_XOFF, int LEAD = R3_LEAD, bool UP = false>
 struct Res3Cfg {
   static constexpr int RP_W = GEO == 0 ? 256 : (GEO == 1 ? 192 : 128);
   static constexpr int RP_BN = RP_W - 2 * LEAD;
@@ -76,7 +77,7 @@ struct Res3Cfg {
   static_assert(GEO == 4 || ROWS::PITCH == S::ROWB, "the padded layout is the scheme's own row");
   static constexpr int LDSB = NC * PR * ROWS::PITCH;
   // with red and bsm: what a workgroup takes of the CU's 160 KB
-  static constexpr int LDS_TOTAL = LDSB + 2 * NW * 4 + NCV * C * 4;
+  static constexpr int LDS_TOTAL = LDSB + 2 * NW * 4 + (NCV + UP) * C * 4;
   static_assert(GEO != 4 || LDS_TOTAL <= 80 * 1024, "GEO 4: two workgroups per CU");
   static_assert(TM >= 1 && TM * WM * 32 == C && TN * WN * 32 == RP_W, "geometry");
 };
@@ -88,7 +89,7 @@ struct Res3Cfg {
 #define RB3_W64 2  // A/B build option: waves per SIMD requested for the 64-channel 128-column block
 #endif
 // PL: ResBlock3Args::planes (the bf16 scheme: 0, or bf16 x and z planes; x stays fp32 in registers)
-template <class S, int C, int GEO, int K, int NCV, int XO, int LEAD, int PL = 0>
+template <class S, int C, int GEO, int K, int NCV, int XO, int LEAD, int PL = 0, bool UP = false>
 __global__ __launch_bounds__((Res3Cfg<S, C, GEO, K, NCV, XO, LEAD>::NT))
 __attribute__((amdgpu_waves_per_eu(S::NP == 1 && RB3_W_B1 > 0 ? RB3_W_B1
                                                                 : (C == 64 && GEO == 2 ? RB3_W64 : (C == 32 || GEO >= 3 ? 2 : 1)))))
@@ -96,9 +97,10 @@ void resblock3_kernel(ResBlock3Args a) {
   constexpr bool XB = (PL & kPlaneXB16) != 0, YB = (PL & kPlaneYB16) != 0;
   using PX = PlaneT<XB>;
   using PY = PlaneT<YB>;
-  using P = Res3Cfg<S, C, GEO, K, NCV, XO, LEAD>;
+  using P = Res3Cfg<S, C, GEO, K, NCV, XO, LEAD, UP>;
   using ROWS = typename P::ROWS;
   static_assert(NCV == 6 || NCV == 2, "ResBlock1 (6 convs) or ResBlock2 (2 convs)");
+  static_assert(!UP || (NCV == 6 && S::SCALED && PL == 0), "the upsampling tail: ResBlock1, f16x3, fp32 planes");
   constexpr int NP = S::NP;
   constexpr bool H3 = S::SCALED;
   constexpr int TM = P::TM, TN = P::TN, NC = P::NC, PR = P::PR, RP_W = P::RP_W;
@@ -106,7 +108,7 @@ void resblock3_kernel(ResBlock3Args a) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[P::LDSB];
   constexpr int NT = P::NT;
   __shared__ float red[2][P::NW];  // double-buffered: consecutive tile_exp calls use different halves
-  __shared__ float bsm[NCV * C];  // the conv biases (read by every epilogue: LDS, not L2, latency)
+  __shared__ float bsm[(NCV + UP) * C];  // the conv biases (read by every epilogue: LDS, not L2, latency)
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -150,6 +152,12 @@ void resblock3_kernel(ResBlock3Args a) {
         const int e = tid + j * NT;
         bl[i][j] = e < C ? a.bias[i][e] : 0.f;
       }
+    float blu[BPT];  // UP: the upsampler's bias
+#pragma unroll
+    for (int j = 0; j < BPT; ++j) {
+      const int e = tid + j * NT;
+      blu[j] = UP && e < C ? a.up_bias[e] : 0.f;
+    }
     f32x4 xv[NC][UG];
 #pragma unroll
     for (int g = 0; g < NC; ++g)
@@ -218,19 +226,28 @@ void resblock3_kernel(ResBlock3Args a) {
         const int e = tid + j * NT;
         if (e < C) bsm[i * C + e] = bl[i][j];
       }
+    if constexpr (UP) {
+#pragma unroll
+      for (int j = 0; j < BPT; ++j) {
+        const int e = tid + j * NT;
+        if (e < C) bsm[NCV * C + e] = blu[j];
+      }
+    }
   }
   __syncthreads();
 
   f32x16 acc[TM][TN];
   f32x4 ar[PD + 1][TM][NP], bcur[TN][NP], bnext[TN][NP];
   rsrc_t ra[TM];
-  auto conv = [&](int wi, int roff, int kstep) __attribute__((always_inline)) {
+  // KT taps (the block's K; 2 for the upsampling tail) of the packed conv at wp
+  auto conv_k = [&](const float* wp, int roff, int kstep, auto ktag) __attribute__((always_inline)) {
+    constexpr int KT = decltype(ktag)::value;
     // swizzled rows: an operand address costs a few VALU per (g, k) and is no immediate offset.
     // Keep the convs2 call (roff 0, kstep 1 in every iteration) from having its 48 addresses
     // hoisted out of the iteration loop, where they would live across the whole kernel
     if constexpr (ROWS::SWIZZLED) asm volatile("" : "+s"(roff), "+s"(kstep));
 #pragma unroll
-    for (int m = 0; m < TM; ++m) ra[m] = make_rsrc(a.w[wi] + ((size_t)(wm * TM + m) * NC * K) * (NP * 256), 0xFFFFFFFFu);
+    for (int m = 0; m < TM; ++m) ra[m] = make_rsrc(wp + ((size_t)(wm * TM + m) * NC * KT) * (NP * 256), 0xFFFFFFFFu);
 #pragma unroll
     for (int m = 0; m < TM; ++m)
 #pragma unroll
@@ -255,15 +272,15 @@ void resblock3_kernel(ResBlock3Args a) {
 #pragma unroll
     for (int g = 0; g < NC; ++g) {
 #pragma unroll
-      for (int k = 0; k < K; ++k) {
-        const int st = g * K + k;
+      for (int k = 0; k < KT; ++k) {
+        const int st = g * KT + k;
 #pragma unroll
         for (int m = 0; m < TM; ++m)
 #pragma unroll
           for (int q = 0; q < NP; ++q)
             ar[PD][m][q] = bload4(ra[m], avoff, (unsigned)((st + PD) * NP + q) * 1024u);
-        const bool more = (k + 1 < K) || (g + 1 < NC);
-        if (more) read_b((k + 1 < K) ? g : g + 1, (k + 1 < K) ? k + 1 : 0, bnext);
+        const bool more = (k + 1 < KT) || (g + 1 < NC);
+        if (more) read_b((k + 1 < KT) ? g : g + 1, (k + 1 < KT) ? k + 1 : 0, bnext);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int e = 0; e < S::NPROD; ++e)
@@ -286,6 +303,9 @@ void resblock3_kernel(ResBlock3Args a) {
         }
       }
     }
+  };
+  auto conv = [&](int wi, int roff, int kstep) __attribute__((always_inline)) {
+    conv_k(a.w[wi], roff, kstep, std::integral_constant<int, K>{});
   };
   // block max of |v| over this workgroup (f16x3 scale exponent); every wave must call it.  The
   // red halves alternate per call, and the store_pieces barrier between two calls separates a
@@ -418,6 +438,126 @@ void resblock3_kernel(ResBlock3Args a) {
     if (H3 && a.amax_out) publish_amax(a.amax_out, b, vmax);
   };
 
+  // UP, the block's last conv as the stage's last MRF launch: v = the MRF mean over the block's x
+  // and the other branches' planes, in the association the z plane's writers use (zmode 2 then 3:
+  // (x + p0) + p1, divided by zdiv), kept in registers; lrelu(v) is staged like every other
+  // operand (the tile's own scale, zeros outside the valid columns and [0, T)) and the next
+  // stage's x2 ConvTranspose1d runs on it as a K = 2 conv: row rho = 2 co + s of column mm reads
+  // v[mm - 1], v[mm] and is sample 2 mm + s - 1 of channel co (convT_epilogue, U = 2).  Columns
+  // mm in [t0, t0 + RP_BN) are this workgroup's, and mm = T is the last workgroup's as well: both
+  // of its taps are valid there (one spare valid column on either side of the kept ones,
+  // resblock3_up_supported)
+  auto final_up = [&](int ci) __attribute__((always_inline)) {
+    const float sc = ldexpf(1.f, ex + a.w_exp[ci]);
+    const float* bs = bsm + ci * C;
+    const int nzp = a.nzp;
+    const float zdiv = a.zdiv;
+    rsrc_t rp[2];
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+      rp[p] = make_rsrc(p < nzp ? a.zp[p] + (size_t)b * C * T : a.x, p < nzp ? (unsigned)C * chb : 0u);
+    float vmax = 0.f;
+#pragma unroll
+    for (int m = 0; m < TM; ++m) {
+      float bv[16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) bv[r] = bs[mrow0 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * half];
+#pragma unroll
+      for (int n = 0; n < TN; ++n) {
+        const int col = xcol0 + n * 32;
+        const int t = tx0 + col;
+        const bool tok = t >= 0 && t < T;
+        const unsigned vlane = tok ? (unsigned)(4 * half) * chb + (unsigned)t * 4u : OOB_OFF;
+        // the other branches' values, one accumulator block at a time: 32 registers, where the
+        // gathers of every block at once would not fit beside acc and x (GEO 4: 128 of 256)
+        __builtin_amdgcn_sched_barrier(0);
+        float pv[2][16];
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            pv[p][r] = bload(rp[p], vlane, (unsigned)(mrow0 + m * 32 + (r & 3) + 8 * (r >> 2)) * chb);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          float v = (acc[m][n][r] * sc + bv[r]) + xr[m][n][r];
+          if (nzp >= 1) v = v + pv[0][r];
+          if (nzp >= 2) v = v + pv[1][r];
+          // the branches' sum, formed here: left to itself the compiler sinks the additions into
+          // the pass below and keeps all 128 gathered values alive until then (60 spilt at GEO 4)
+          asm volatile("" : "+v"(v));
+          xr[m][n][r] = v;  // the conv's accumulators are dead from here
+        }
+      }
+    }
+    // the mean and the staged value in a pass of its own: the division's temporaries then sit in
+    // the accumulators' registers instead of beside them (GEO 4 spilt 58 registers otherwise)
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int m = 0; m < TM; ++m)
+#pragma unroll
+      for (int n = 0; n < TN; ++n) {
+        const int col = xcol0 + n * 32;
+        const int t = tx0 + col;
+        const bool ok = col >= lo && col < hi && t >= 0 && t < T;
+        __builtin_amdgcn_sched_barrier(0);  // 16 divisions in flight, not 64
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          float v = xr[m][n][r];
+          if (nzp >= 1) v = v / zdiv;
+          v = ok ? lrelu2(v, 0.1f) : 0.f;
+          acc[m][n][r] = v;
+          vmax = fmaxf(vmax, fabsf(v));
+        }
+      }
+    const int e2 = tile_exp(vmax);
+    store_pieces(XO, ldexpf(1.f, -e2));
+    __syncthreads();
+    ex = e2;
+    conv_k(a.up_w, XO - 1, 1, std::integral_constant<int, 2>{});  // taps at X rows column - 1 + k
+    const float sc2 = ldexpf(1.f, ex + a.up_w_exp);
+    const float* bu = bsm + NCV * C;
+    const int To = 2 * T;
+    const unsigned chby = (unsigned)To * 4u;
+    const rsrc_t ry = make_rsrc(a.up_y + (size_t)b * (C / 2) * To, (unsigned)(C / 2) * chby);
+    // column T is the last workgroup's alone: in the one before it, it can lie on the grid too,
+    // but past the valid columns
+    const bool last_wg = blockIdx.x == gridDim.x - 1;
+    float umax = 0.f;
+#pragma unroll
+    for (int m = 0; m < TM; ++m) {
+      float bv[16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) bv[r] = bu[mrow0 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * half];
+#pragma unroll
+      for (int n = 0; n < TN; ++n) {
+        const int col = xcol0 + n * 32;
+        const int mm = tx0 + col;
+        const bool keep = col >= LEAD && mm <= T && (col < LEAD + P::RP_BN || (mm == T && last_wg));
+        const int ts = 2 * mm - 1;  // registers r, r + 1 (r even): samples ts, ts + 1 of channel rho / 2
+        const unsigned vl = (unsigned)(2 * half) * chby + (unsigned)ts * 4u;
+#pragma unroll
+        for (int r = 0; r < 16; r += 2) {
+          const unsigned so = (unsigned)((mrow0 + m * 32) / 2 + ((r & 3) >> 1) + 4 * (r >> 2)) * chby;
+          const float v0 = acc[m][n][r] * sc2 + bv[r];
+          const float v1 = acc[m][n][r + 1] * sc2 + bv[r + 1];
+          if (keep && ts >= 0 && ts + 1 < To) {
+            umax = fmaxf(umax, fmaxf(fabsf(v0), fabsf(v1)));
+            const f32x2 v = {v0, v1};
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_t, v), ry, (int)vl, (int)so, TTS_ST_POL);
+          } else {
+            // the pair straddles the plane's start (mm = 0) or end (mm = T)
+            const bool k0 = keep && ts >= 0, k1 = keep && ts + 1 < To;
+            if (k0) umax = fmaxf(umax, fabsf(v0));
+            if (k1) umax = fmaxf(umax, fabsf(v1));
+            bstore(ry, v0, k0 ? vl : OOB_OFF, so);
+            bstore(ry, v1, k1 ? vl + 4u : OOB_OFF, so);
+          }
+        }
+      }
+    }
+    if (a.up_amax) publish_amax(a.up_amax, b, umax);
+  };
+
   if constexpr (NCV == 6) {
     // one ResBlock1 iteration; LAST 0: the last one is told at run time (one loop body), 1 / 2:
     // known not to be / to be the last
@@ -462,9 +602,10 @@ void resblock3_kernel(ResBlock3Args a) {
       lo += HK;
       hi -= HK;
       if (LAST == 1 || (LAST == 0 && it < 2)) residual_to_lds(2 * it + 1);
+      else if constexpr (UP) final_up(2 * it + 1);
       else final_to_z(2 * it + 1);
     };
-    if constexpr (GEO == 4) {
+    if constexpr (GEO == 4 || UP) {
       // the 256-register form peels the last iteration: with the z epilogue inside the loop body
       // the compiler carries the residual x in two register sets and spills one block of it
 #pragma unroll 1

@@ -8,7 +8,8 @@
 //   ds_write_b64   4 groups of 16 contiguous lanes; bank = (byte / 4) mod 32
 // Asserted for the swizzled 64-byte rows: the unit map is a bijection within every row, piece()
 // and the + 16 j rows rule agree with off(); every read group touches 64 distinct banks for the
-// taps of dilations 1, 3, 5 (convs1: rows column + 5 + (k - 1) d) and of convs2 (rows column + k);
+// taps of dilations 1, 3, 5 (convs1: rows column + 5 + (k - 1) d), of convs2 (rows column + k) and
+// of the upsampling tail's two-tap conv (rows column + 4 + k);
 // every store group is at most 2-way conflicted (store_xt8 at row offsets 5 and 1, and the
 // prologue's 8-byte stores).  The padded rows are replayed too and must be conflict-free
 // everywhere, which checks the replay itself against the layout the kernels have always used.
@@ -105,15 +106,16 @@ static void check_accesses(const char* name, int max_store) {
   const auto w8 = contiguous_groups(8), w16 = contiguous_groups(16);
   std::vector<int> addr(64);
   // read_b: row = g PR + xcol0 + 32 n + roff + k kstep, unit half + 2 q
-  struct Tap { int roff, kstep; };
+  struct Tap { int roff, kstep, ntaps; };
   std::vector<Tap> taps;
-  for (int d : {1, 3, 5}) taps.push_back({XO - HK * d, d});  // convs1 on X rows
-  taps.push_back({0, 1});                                     // convs2 on xt rows
+  for (int d : {1, 3, 5}) taps.push_back({XO - HK * d, d, 3});  // convs1 on X rows
+  taps.push_back({0, 1, 3});                                     // convs2 on xt rows
+  taps.push_back({XO - 1, 1, 2});  // the upsampling tail's K = 2 conv on X rows: columns c - 1, c
   for (const Tap& t : taps)
     for (int g = 0; g < NC; ++g)
       for (int wn = 0; wn < 2; ++wn)
         for (int n = 0; n < 2; ++n)
-          for (int k = 0; k < 3; ++k)
+          for (int k = 0; k < t.ntaps; ++k)
             for (int q = 0; q < NP; ++q) {
               for (int lane = 0; lane < 64; ++lane) {
                 const int row = g * PR + wn * 64 + (lane & 31) + n * 32 + t.roff + k * t.kstep;
