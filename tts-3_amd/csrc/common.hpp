@@ -118,7 +118,8 @@ struct ResPairArgs {
 bool resblock_pair_supported(int mode, int C, int K, int dil);
 bool resblock_pair_preferred(int mode, int C, int K, int dil);  // supported and measured faster
 bool resblock_pair128(int mode, int C, int K);  // bf16: 128-channel k7 / k11 iterations as pairs
-void launch_resblock_pair(int mode, const ResPairArgs& a, int B, int K, int C, hipStream_t s);
+// wide64: see mrf_geo64_wide below
+void launch_resblock_pair(int mode, const ResPairArgs& a, int B, int K, int C, int wide64, hipStream_t s);
 
 // A whole kernel-3 ResBlock1 (three iterations, six convs) in one kernel (kernels_resblock.hip):
 // x stays in registers between iterations (residual), lrelu(x) and xt pass through LDS.
@@ -151,8 +152,14 @@ struct ResBlock3Args {
 bool resblock3_supported(int mode, int C, int K, const int* dil);
 // the upsampling tail (ResBlock3Args::up_w): f16x3, kernel 3 at 64 / 128 channels, and a valid
 // column to spare on either side of the kept ones (the tail's K = 2 taps read z one column back)
-bool resblock3_up_supported(int mode, int C, int K, const int* dil);
-void launch_resblock3(int mode, const ResBlock3Args& a, int B, int C, int K, hipStream_t s);
+bool resblock3_up_supported(int mode, int C, int K, const int* dil, int wide64);
+// wide64 (mrf_geo64_wide): f16x3 at 64 channels takes 256-column tiles on swizzled 64-byte LDS rows
+// (the kernel-3 block keeps 232 columns per workgroup instead of 104, a pair 256 - (K - 1) instead
+// of 192 - (K - 1)); 0: the narrow tiles
+constexpr int kWide64Block = 1, kWide64Pair = 2;
+void launch_resblock3(int mode, const ResBlock3Args& a, int B, int C, int K, int wide64, hipStream_t s);
+// both bits for f16x3 unless TTS_MI355X_GEO64_WIDE=0; read when an executor is created
+int mrf_geo64_wide(int mode);
 // A whole ResBlock2 (hifigan_generator.py:150-155: two convs of kernel K, dilations dil[0..1],
 // each x = conv(lrelu(x)) + x) in one kernel; ResBlock3Args with w / bias / w_exp[0..1].
 // geo64 = 1: 192-column tiles at C = 64 (default 128)

@@ -112,6 +112,7 @@ Hifigan::Hifigan(const TtsHifiganCfg& cfg, const float* const* hw, int device)
   const char* sb = std::getenv("TTS_MI355X_SUBBATCH");
   n_lanes_ = sb ? std::max(1, std::min(std::atoi(sb), 8)) : 2;
   rb2_geo64_ = resblock2_geo64(mode);
+  geo64_wide_ = mrf_geo64_wide(mode);
   // bf16 planes: every MRF stage length is then a multiple of 8 (the Winograd DMA's 16-byte rows)
   const char* bp = std::getenv("TTS_MI355X_BF16_PLANES");
   planes16_ = mode == MATH_BF16 && !(bp && bp[0] == '0') && cfg_.num_upsamples >= 1 &&
@@ -247,7 +248,7 @@ Hifigan::Hifigan(const TtsHifiganCfg& cfg, const float* const* hw, int device)
       const ConvTile t = conv_tile(u.mode, u.tile);
       const bool tile_ok = !t.WINO && t.CK % 16 == 0 && ch % t.CK == 0 && ch % t.BM == 0;
       ups_fused_[i] = tile_ok && resblock3_up_supported(mode, ch, cfg_.resblock_kernel_sizes[0],
-                                                        cfg_.resblock_dilation_sizes[0]);
+                                                        cfg_.resblock_dilation_sizes[0], geo64_wide_);
     }
   }
   const float* post_w = hw[wi]; wi += 1;
@@ -697,7 +698,7 @@ void Hifigan::forward_plain(const float* mel, int B, int C, int T, int pad, cons
         const double bytes = 4.0 * B * L1.Cout * (double)len * (K + 1) + 4.0 * 6.0 * L1.Cout * L1.Cin * L1.K +
                              4.0 * Un.Cin * Un.Cout * 2 * Un.U;
         const std::string nm = "mrf_block_k" + std::to_string(L1.K) + "_c" + std::to_string(L1.Cout);
-        run(prof, s, nm.c_str(), flops, bytes, [&] { launch_resblock3(L1.mode, ra, B, L1.Cout, L1.K, s); });
+        run(prof, s, nm.c_str(), flops, bytes, [&] { launch_resblock3(L1.mode, ra, B, L1.Cout, L1.K, geo64_wide_, s); });
         std::swap(bufO, bufT0);  // the next stage reads what was T; the old O is its stream-0 T
       } else if (cfg_.resblock_type == 1 && rb.fused3) {
         // the three iterations in one launch: o -> MRF z
@@ -715,7 +716,7 @@ void Hifigan::forward_plain(const float* mel, int B, int C, int T, int pad, cons
                              4.0 * 6.0 * L1.Cout * L1.Cin * L1.K;
         const std::string nm = "mrf_block_k" + std::to_string(L1.K) + "_c" + std::to_string(L1.Cout);
         zorder();
-        run(prof, sj, nm.c_str(), flops, bytes, [&] { launch_resblock3(L1.mode, ra, B, L1.Cout, L1.K, sj); });
+        run(prof, sj, nm.c_str(), flops, bytes, [&] { launch_resblock3(L1.mode, ra, B, L1.Cout, L1.K, geo64_wide_, sj); });
         zdone();
       } else if (cfg_.resblock_type == 1 && rb.fused) {
         // x_{m+1} = convs2[m](lrelu(convs1[m](lrelu(x_m)))) + x_m in one launch per m; the
@@ -759,7 +760,7 @@ void Hifigan::forward_plain(const float* mel, int B, int C, int T, int pad, cons
           const std::string nm = std::string(post ? "mrf_pair_post_k" : "mrf_pair_k") + std::to_string(L1.K) +
                                  "_c" + std::to_string(L1.Cout);
           if (last) zorder();
-          run(prof, sj, nm.c_str(), flops, bytes, [&] { launch_resblock_pair(L1.mode, pa, B, L1.K, L1.Cout, sj); });
+          run(prof, sj, nm.c_str(), flops, bytes, [&] { launch_resblock_pair(L1.mode, pa, B, L1.K, L1.Cout, geo64_wide_, sj); });
           if (last) zdone();
         }
       } else if (cfg_.resblock_type == 1) {

@@ -41,12 +41,25 @@ namespace tts {
 //   on its CU, so the second wave per SIMD is what hides one wave's staging, hand-off and epilogue
 //   latencies.  GEO 7 / 8 (the bf16 defaults): the same with waves of 32 rows x 128 columns (4 x 2
 //   on 256 columns, 8 x 1 on 128), so a weight fragment feeds 4 MFMAs.
+// SWZ (f16x3, C = 64, with GEO 0): the staged rows are the swizzled 64-byte rows of res3_layout.hpp
+// instead of the padded 80-byte ones.  GEO 0's 256 columns then take 4 x 306 x 64 = 78,336 B at
+// kernel 11 (the all-at-once X window; xt: 4 x 288 x 64 = 73,728 B) where the padded rows take
+// 97,920 B, so two workgroups share a CU as they do at GEO 1, with 64 x 64 wave tiles: an
+// activation fragment feeds 2 MFMAs instead of 1, and K - 1 of 256 columns are halo instead of
+// K - 1 of 192.  Every LDS address of the staged operands is base + ROWS::off(row, unit) with the
+// row counted inside its buffer (X window c, xt group g) and a base that is a multiple of the
+// pitch: a multiple of 64 bytes moves every row by whole rows of banks, so the bank behaviour of
+// res3_layout.hpp holds for each buffer (tests_native/geo64_layout_check.cpp replays it).
 
 constexpr int kPostK = 7;     // conv_post kernel (hifigan_generator.py:229-230)
 constexpr int kPostHalo = 3;  // its zero-padding halo per side
 
-template <class S, int K, int C, int PD, int GEO, bool ALLX = false, bool POST = false>
+template <class S, int K, int C, int PD, int GEO, bool ALLX = false, bool POST = false, bool SWZ = false>
 struct PairCfg {
+  static_assert(!SWZ || (GEO == 0 && C == 64 && S::NP == 2 && ALLX), "SWZ: GEO 0 at 64 channels, two-piece rows");
+  using ROWS = Res3Rows<S::NP, SWZ>;
+  static constexpr int PITCH = ROWS::PITCH;       // S::ROWB, or 64 (SWZ)
+  static_assert(SWZ || PITCH == S::ROWB, "the padded layout is the scheme's own row");
   static constexpr int RP_W = (GEO == 0 || GEO == 4 || GEO == 5 || GEO == 7) ? 256 : (GEO == 1 ? 192 : 128);
   static constexpr int LEAD = (K - 1) / 2;        // xt row 0 holds time t0 - LEAD (conv2's halo)
   static constexpr int RP_BN = RP_W - 2 * LEAD;
@@ -61,9 +74,9 @@ struct PairCfg {
   static constexpr int NC = C / 16;               // 16-channel groups
   static constexpr int HMAX = (K - 1) * 5;        // dilation <= 5
   static constexpr int XROWS = RP_W + HMAX;
-  static constexpr int XSZB = XROWS * S::ROWB;    // one X staging buffer (16 channels)
+  static constexpr int XSZB = XROWS * PITCH;      // one X staging buffer (16 channels)
   static constexpr int TROWS = RP_W + 32;         // + zero rows read by the discarded columns
-  static constexpr int TSZB = NC * TROWS * S::ROWB;
+  static constexpr int TSZB = NC * TROWS * PITCH;
   // ALLX: every 16-channel group of the input window is staged at once (one HBM latency for the
   // whole of phase 1, no per-chunk barriers); otherwise double-buffered per group
   static constexpr int XBUFS = ALLX ? NC : 2;
@@ -74,6 +87,9 @@ struct PairCfg {
   // POST: output tiles overlap by conv_post's halo on both sides
   static constexpr int STRIDE = POST ? RP_BN - 2 * kPostHalo : RP_BN;
   static constexpr int UPT = (XROWS * 4 + NT - 1) / NT;
+  // with red, the biases and conv_post's weights: what a workgroup takes of the CU's 160 KB
+  static constexpr int LDS_TOTAL = LDSB + NW * 4 + 2 * C * 4 + (POST ? C * kPostK : 1) * 4;
+  static_assert(!SWZ || LDS_TOTAL <= 80 * 1024, "SWZ: two workgroups per CU");
   static_assert(TM >= 1 && TM * WM * 32 == C && TN * WN * 32 == RP_W, "geometry");
 };
 
@@ -83,14 +99,15 @@ struct PairCfg {
 #ifndef PAIR_W_B1
 #define PAIR_W_B1 3  // waves per SIMD asked of the bf16 scheme's pair kernels (0: as the others; 3 measured -1% per bf16 step, profiles/ab_r06_bf16_occupancy.txt)
 #endif
-template <class S, int K, int C, int PD, int GEO, bool ALLX, bool POST = false, int PL = 0>
+template <class S, int K, int C, int PD, int GEO, bool ALLX, bool POST = false, int PL = 0, bool SWZ = false>
 __global__ __launch_bounds__((PairCfg<S, K, C, PD, GEO, ALLX, POST>::NT)) __attribute__((amdgpu_waves_per_eu(
-    C > 64 ? (GEO >= 5 ? 2 : 1) : (S::NP == 1 && PAIR_W_B1 > 0 ? PAIR_W_B1 : ((C == 32 || GEO == 2) && S::ROWB <= 80 ? 3 : 1)))))
+    SWZ ? 2 : C > 64 ? (GEO >= 5 ? 2 : 1) : (S::NP == 1 && PAIR_W_B1 > 0 ? PAIR_W_B1 : ((C == 32 || GEO == 2) && S::ROWB <= 80 ? 3 : 1)))))
 void resblock_pair_kernel(ResPairArgs pa) {
   constexpr bool XB = (PL & kPlaneXB16) != 0, YB = (PL & kPlaneYB16) != 0;
   using PX = PlaneT<XB>;
   using PY = PlaneT<YB>;
-  using P = PairCfg<S, K, C, PD, GEO, ALLX, POST>;
+  using P = PairCfg<S, K, C, PD, GEO, ALLX, POST, SWZ>;
+  using ROWS = typename P::ROWS;
   constexpr int RP_W = P::RP_W, RP_BN = P::RP_BN;
   constexpr int NP = S::NP;
   constexpr bool H3 = S::SCALED;
@@ -197,7 +214,9 @@ void resblock_pair_kernel(ResPairArgs pa) {
     const int ts = tx0 - a1.pad + r;
     const bool ok = r < XW && ts >= 0 && ts < T;
     uvoff[i] = ok ? (unsigned)(4 * q) * chb + (unsigned)ts * PX::ES : OOB_OFF;
-    ulds[i] = r < XW ? r * S::ROWB + 8 * quad_pos(q) : -1;
+    // channel quad q sits at position 4 quad_pos(q): unit quad_pos(q) / 2, its low or high 8 bytes
+    const int qp = quad_pos(q);
+    ulds[i] = r < XW ? ROWS::off(r, qp >> 1) + 8 * (qp & 1) : -1;
   }
   f32x4 xall[ALLX ? NC : 1][P::UPT];
   auto load_x = [&](int c) {
@@ -220,7 +239,10 @@ void resblock_pair_kernel(ResPairArgs pa) {
           v[j] = lrelu2(xreg[i][j], a1.in_slope);
           if (H3) v[j] *= xscale;
         }
-        split_store4<S>(xl + ulds[i], v[0], v[1], v[2], v[3]);
+        unsigned char* dst[NP];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) dst[p] = xl + ROWS::piece(ulds[i], p);
+        split_store4<S>(dst, v[0], v[1], v[2], v[3]);
       }
     }
   };
@@ -263,9 +285,11 @@ void resblock_pair_kernel(ResPairArgs pa) {
   auto read_x = [&](const unsigned char* xl, int k, f32x4 (*dst)[NP]) {
 #pragma unroll
     for (int n = 0; n < TN; ++n) {
-      const unsigned char* p = xl + (xrow0 + n * 32 + k * d) * S::ROWB + 16 * half;
+      // 32 n rows further on: the same unit map (res3_layout.hpp)
+      const int o = ROWS::off(xrow0 + k * d, half);
 #pragma unroll
-      for (int q = 0; q < NP; ++q) dst[n][q] = *reinterpret_cast<const f32x4*>(p + 32 * q);
+      for (int q = 0; q < NP; ++q)
+        dst[n][q] = *reinterpret_cast<const f32x4*>(xl + ROWS::piece(o, q) + n * 32 * P::PITCH);
     }
   };
 
@@ -356,14 +380,20 @@ void resblock_pair_kernel(ResPairArgs pa) {
 #pragma unroll
       for (int n = 0; n < TN; ++n)
 #pragma unroll
-        for (int gl = 0; gl < 2; ++gl)
-          store_xt8<S>(smem + (((mrow0 + m * 32) / 16 + gl) * P::TROWS + xrow0 + n * 32) * S::ROWB + 16 * half,
-                       acc[m][n], 8 * gl, tscale);
-    // zero rows RP_W .. TROWS-1 of every group (read only by the discarded columns)
-    constexpr int ZB = (P::TROWS - RP_W) * S::ROWB;  // bytes per group
+        for (int gl = 0; gl < 2; ++gl) {
+          const int o = ROWS::off(xrow0, half);
+          unsigned char* dst[NP];
+#pragma unroll
+          for (int p = 0; p < NP; ++p)
+            dst[p] = smem + (((mrow0 + m * 32) / 16 + gl) * P::TROWS + n * 32) * P::PITCH + ROWS::piece(o, p);
+          store_xt8<S>(dst, acc[m][n], 8 * gl, tscale);
+        }
+    // zero rows RP_W .. TROWS-1 of every group (read only by the discarded columns); whole rows,
+    // so only the pitch matters
+    constexpr int ZB = (P::TROWS - RP_W) * P::PITCH;  // bytes per group
     for (int e = tid * 16; e < NC * ZB; e += NT * 16) {
       const int g = e / ZB;
-      *reinterpret_cast<f32x4*>(smem + (g * P::TROWS + RP_W) * S::ROWB + (e - g * ZB)) = f32x4{};
+      *reinterpret_cast<f32x4*>(smem + (g * P::TROWS + RP_W) * P::PITCH + (e - g * ZB)) = f32x4{};
     }
     __syncthreads();
     // ---------------------------------------------------------------- phase 2: convs2 from LDS
@@ -384,9 +414,10 @@ void resblock_pair_kernel(ResPairArgs pa) {
     auto read_t = [&](int g, int k, f32x4 (*dst)[NP]) {
 #pragma unroll
       for (int n = 0; n < TN; ++n) {
-        const unsigned char* p = smem + (g * P::TROWS + trow0 + n * 32 + k) * S::ROWB + 16 * half;
+        const int o = ROWS::off(trow0 + k, half);
 #pragma unroll
-        for (int q = 0; q < NP; ++q) dst[n][q] = *reinterpret_cast<const f32x4*>(p + 32 * q);
+        for (int q = 0; q < NP; ++q)
+          dst[n][q] = *reinterpret_cast<const f32x4*>(smem + (g * P::TROWS + n * 32) * P::PITCH + ROWS::piece(o, q));
       }
     };
     read_t(0, 0, bcur);
@@ -427,7 +458,7 @@ void resblock_pair_kernel(ResPairArgs pa) {
 }
 
 namespace {
-template <class S, int K, int C, int GEO>
+template <class S, int K, int C, int GEO, bool SWZ = false>
 void launch_pair_t(const ResPairArgs& a, int B, hipStream_t s) {
   // all-at-once staging measured faster at 64 channels (-7% on k3), not at 32; GEO 2 double-buffers
   // (the LDS of three workgroups per CU)
@@ -436,15 +467,15 @@ void launch_pair_t(const ResPairArgs& a, int B, hipStream_t s) {
   auto go = [&](auto pl_tag) {
     constexpr int PL = decltype(pl_tag)::value;
     if (a.post_w) {
-      using P = PairCfg<S, K, C, PD, GEO, AX, true>;
+      using P = PairCfg<S, K, C, PD, GEO, AX, true, SWZ>;
       static_assert(P::RP_BN - 2 * kPostHalo <= 256, "one conv_post column per thread");
       dim3 grid(ceil_div(a.c1.Tout, P::STRIDE), 1, B);
-      hipLaunchKernelGGL((resblock_pair_kernel<S, K, C, PD, GEO, AX, true, PL>), grid, dim3(P::NT), 0, s, a);
+      hipLaunchKernelGGL((resblock_pair_kernel<S, K, C, PD, GEO, AX, true, PL, SWZ>), grid, dim3(P::NT), 0, s, a);
       return;
     }
-    using P = PairCfg<S, K, C, PD, GEO, AX>;
+    using P = PairCfg<S, K, C, PD, GEO, AX, false, SWZ>;
     dim3 grid(ceil_div(a.c1.Tout, P::RP_BN), 1, B);
-    hipLaunchKernelGGL((resblock_pair_kernel<S, K, C, PD, GEO, AX, false, PL>), grid, dim3(P::NT), 0, s, a);
+    hipLaunchKernelGGL((resblock_pair_kernel<S, K, C, PD, GEO, AX, false, PL, SWZ>), grid, dim3(P::NT), 0, s, a);
   };
   if (a.c1.planes != 0) {
     // bf16 activation planes: x, x' and z all bf16 (the bf16 scheme)
@@ -466,7 +497,7 @@ int pair_geo64() {
 }
 
 template <class S, int K>
-void launch_pair_k(const ResPairArgs& a, int B, int C, hipStream_t s) {
+void launch_pair_k(const ResPairArgs& a, int B, int C, int wide64, hipStream_t s) {
   if constexpr (S::NP == 1) {
     // bf16 only: 128 channels on 256 columns, one wave per SIMD (4 x 32 rows x 64 columns of
     // accumulators per wave), the xt buffer 8 groups x 288 rows x 48 B = 111 KB (the 16-bit-pair
@@ -506,6 +537,14 @@ void launch_pair_k(const ResPairArgs& a, int B, int C, hipStream_t s) {
       return;
     }
   }
+  // C = 64, f16x3: GEO 0's 256 columns on swizzled rows (two workgroups per CU) unless
+  // TTS_MI355X_GEO64_WIDE=0 or TTS_MI355X_PAIR_GEO64 asks for another geometry
+  if constexpr (std::is_same<S, SchemeH3>::value) {
+    if (C == 64 && (wide64 & kWide64Pair) && pair_geo64() == 1 && a.c1.planes == 0) {
+      launch_pair_t<S, K, 64, 0, true>(a, B, s);
+      return;
+    }
+  }
   if (C == 32) launch_pair_t<S, K, 32, 0>(a, B, s);
   else if (C == 64 && pair_geo64() == 2 && S::ROWB <= 80) launch_pair_t<S, K, 64, 2>(a, B, s);
   else if (C == 64 && pair_geo64() == 4 && S::NP == 1) launch_pair_t<S, K, 64, 4>(a, B, s);
@@ -514,11 +553,11 @@ void launch_pair_k(const ResPairArgs& a, int B, int C, hipStream_t s) {
 }
 
 template <class S>
-void launch_pair_s(const ResPairArgs& a, int B, int K, int C, hipStream_t s) {
+void launch_pair_s(const ResPairArgs& a, int B, int K, int C, int wide64, hipStream_t s) {
   switch (K) {
-    case 3: launch_pair_k<S, 3>(a, B, C, s); break;
-    case 7: launch_pair_k<S, 7>(a, B, C, s); break;
-    case 11: launch_pair_k<S, 11>(a, B, C, s); break;
+    case 3: launch_pair_k<S, 3>(a, B, C, wide64, s); break;
+    case 7: launch_pair_k<S, 7>(a, B, C, wide64, s); break;
+    case 11: launch_pair_k<S, 11>(a, B, C, wide64, s); break;
     default: throw Error(3, "resblock pair: kernel size must be 3, 7 or 11");
   }
 }
@@ -554,7 +593,7 @@ bool resblock_pair_preferred(int mode, int C, int K, int dil) {
   return resblock_pair_supported(mode, C, K, dil);
 }
 
-void launch_resblock_pair(int mode, const ResPairArgs& a, int B, int K, int C, hipStream_t s) {
+void launch_resblock_pair(int mode, const ResPairArgs& a, int B, int K, int C, int wide64, hipStream_t s) {
   TTS_REQUIRE(resblock_pair_supported(mode, C, K, a.c1.dil), 3, "resblock pair: unsupported configuration");
   TTS_REQUIRE(a.c1.Cin == C && a.c1.Cout == C && a.c2.Cin == C && a.c2.Cout == C && a.c1.Tin == a.c1.Tout &&
                   a.c2.Tout == a.c1.Tout && a.c1.rep_pad == 0 && a.c2.dil == 1,
@@ -565,9 +604,9 @@ void launch_resblock_pair(int mode, const ResPairArgs& a, int B, int K, int C, h
   TTS_REQUIRE((int64_t)C * a.c1.Tout * 4 < (int64_t(1) << 31), 3, "resblock pair: plane exceeds 2 GiB");
   TTS_REQUIRE(!a.post_w || (a.c2.zmode == 3 && a.c2.res && a.c2.z && a.wav && !a.c2.mask), 1,
               "resblock pair: the fused conv_post needs the final MRF sum (zmode 3) with a residual");
-  if (mode == MATH_FP32_F16X3) launch_pair_s<SchemeH3>(a, B, K, C, s);
-  else if (mode == MATH_BF16) launch_pair_s<SchemeB1>(a, B, K, C, s);
-  else launch_pair_s<SchemeX6>(a, B, K, C, s);
+  if (mode == MATH_FP32_F16X3) launch_pair_s<SchemeH3>(a, B, K, C, wide64, s);
+  else if (mode == MATH_BF16) launch_pair_s<SchemeB1>(a, B, K, C, 0, s);
+  else launch_pair_s<SchemeX6>(a, B, K, C, 0, s);
   TTS_HIP_CHECK(hipGetLastError());
 }
 
@@ -588,10 +627,21 @@ void launch_res3_up_t(const ResBlock3Args& a, int B, hipStream_t s) {
   dim3 grid(ceil_div(a.T, P::RP_BN), 1, B);
   hipLaunchKernelGGL((resblock3_kernel<S, C, GEO, 3, 6, r3_xoff(3), r3_lead(3), 0, true>), grid, dim3(P::NT), 0, s, a);
 }
+// the 64-channel block on 256 columns (Res3Cfg SW: swizzled rows, 4 waves of 64 x 64), plain and
+// with the upsampling tail
+template <class S, bool UP>
+void launch_res3_wide64(const ResBlock3Args& a, int B, hipStream_t s) {
+  using P = Res3Cfg<S, 64, 0, 3, 6, r3_xoff(3), r3_lead(3), UP, true>;
+  static_assert(P::RP_BN == 232, "kept columns [12, 244)");
+  dim3 grid(ceil_div(a.T, P::RP_BN), 1, B);
+  hipLaunchKernelGGL((resblock3_kernel<S, 64, 0, 3, 6, r3_xoff(3), r3_lead(3), 0, UP, true>), grid, dim3(P::NT), 0, s, a);
+}
 template <class S>
-void launch_res3_s(const ResBlock3Args& a, int B, int C, int K, hipStream_t s) {
-  // C = 64: 128 columns (2 waves/SIMD, a quarter of the columns are halo; 192 columns at one
-  // wave per SIMD measured slower).  C = 128: 128 columns, LDS 8 x 138 rows.  The two-piece scheme
+void launch_res3_s(const ResBlock3Args& a, int B, int C, int K, int wide64, hipStream_t s) {
+  // C = 64: f16x3 takes the 256-column tile on swizzled rows (launch_res3_wide64; 24 of 256 columns
+  // are halo, two workgroups per CU: 2.37 -> 2.26 ms per launch, profiles/ab_geo64_wide.txt).  The
+  // other schemes, and f16x3 with TTS_MI355X_GEO64_WIDE=0, keep 128 columns (2 waves/SIMD, 24 of 128
+  // columns are halo; 192 columns at one wave per SIMD measured slower).  C = 128: 128 columns, LDS 8 x 138 rows.  The two-piece scheme
   // (f16x3) takes GEO 4: 4 waves of 64 rows x 64 columns on swizzled 64-byte rows, 73,760 B, two
   // workgroups per CU (4.28 ms per batch against 4.73 ms for GEO 3, same bits).  bf16 keeps GEO 3,
   // 8 waves of 32 rows x 64 columns, two per SIMD in one workgroup (its 48-byte rows already fit
@@ -606,6 +656,13 @@ void launch_res3_s(const ResBlock3Args& a, int B, int C, int K, hipStream_t s) {
     if (C == 32) launch_res3_t<S, 32, 0, 11>(a, B, s);
     else launch_res3_t<S, 64, 0, 11>(a, B, s);
     return;
+  }
+  // C = 64, f16x3: the 256-column tile on swizzled rows unless TTS_MI355X_GEO64_WIDE=0
+  if constexpr (std::is_same<S, SchemeH3>::value) {
+    if (C == 64 && (wide64 & kWide64Block) && a.planes == 0) {
+      launch_res3_wide64<S, false>(a, B, s);
+      return;
+    }
   }
   if (C == 32) launch_res3_t<S, 32, 0, 3>(a, B, s);
   else if (C == 128) {
@@ -638,11 +695,19 @@ bool resblock3_supported(int mode, int C, int K, const int* dil) {
   return lo <= r3_lead(K);
 }
 
-bool resblock3_up_supported(int mode, int C, int K, const int* dil) {
+int mrf_geo64_wide(int mode) {
+  if (mode != MATH_FP32_F16X3) return 0;
+  const char* e = std::getenv("TTS_MI355X_GEO64_WIDE");
+  // one switch for both parts; each alone was measured with a build that read "block" / "pair"
+  // here (profiles/ab_geo64_wide.txt) and both stayed
+  return e && e[0] == '0' ? 0 : (kWide64Block | kWide64Pair);
+}
+
+bool resblock3_up_supported(int mode, int C, int K, const int* dil, int wide64) {
   if (mode != MATH_FP32_F16X3 || K != 3 || !(C == 64 || C == 128) || !resblock3_supported(mode, C, K, dil)) return false;
   // the valid-range walk again, from both grid edges: output column c of the tail reads z at
   // c - 1 and c, and the last workgroup also emits the column after its kept ones
-  const int rp_w = 128;
+  const int rp_w = C == 64 && (wide64 & kWide64Block) ? 256 : 128;
   int lo = -r3_xoff(K), hi = rp_w + r3_xoff(K);
   for (int m = 0; m < 3; ++m) {
     lo = std::max(lo + dil[m], 0) + 1;
@@ -651,24 +716,25 @@ bool resblock3_up_supported(int mode, int C, int K, const int* dil) {
   return lo <= r3_lead(K) - 1 && hi >= rp_w - r3_lead(K) + 1;
 }
 
-void launch_resblock3(int mode, const ResBlock3Args& a, int B, int C, int K, hipStream_t s) {
+void launch_resblock3(int mode, const ResBlock3Args& a, int B, int C, int K, int wide64, hipStream_t s) {
   TTS_REQUIRE(resblock3_supported(mode, C, K, a.dil), 3, "resblock3: unsupported configuration");
   TTS_REQUIRE((int64_t)C * a.T * 4 < (int64_t(1) << 31), 3, "resblock3: plane exceeds 2 GiB");
   if (a.up_w) {
-    TTS_REQUIRE(resblock3_up_supported(mode, C, K, a.dil), 3, "resblock3: no upsampling tail for this configuration");
+    TTS_REQUIRE(resblock3_up_supported(mode, C, K, a.dil, wide64), 3, "resblock3: no upsampling tail for this configuration");
     TTS_REQUIRE(a.x && a.up_y && a.up_y != a.x && a.up_bias && a.planes == 0 && a.nzp >= 0 && a.nzp <= 2, 1,
                 "resblock3: bad arguments of the upsampling tail");
     for (int p = 0; p < a.nzp; ++p)
       TTS_REQUIRE(a.zp[p] && a.zp[p] != a.up_y, 1, "resblock3: a branch plane is missing or aliases the tail's output");
     if (C == 128) launch_res3_up_t<SchemeH3, 128, 4>(a, B, s);
+    else if (wide64 & kWide64Block) launch_res3_wide64<SchemeH3, true>(a, B, s);
     else launch_res3_up_t<SchemeH3, 64, 2>(a, B, s);
     TTS_HIP_CHECK(hipGetLastError());
     return;
   }
   TTS_REQUIRE(a.zmode >= 1 && a.zmode <= 3 && a.z && a.x && a.x != a.z, 1, "resblock3: bad arguments");
-  if (mode == MATH_FP32_F16X3) launch_res3_s<SchemeH3>(a, B, C, K, s);
-  else if (mode == MATH_BF16) launch_res3_s<SchemeB1>(a, B, C, K, s);
-  else launch_res3_s<SchemeX6>(a, B, C, K, s);
+  if (mode == MATH_FP32_F16X3) launch_res3_s<SchemeH3>(a, B, C, K, wide64, s);
+  else if (mode == MATH_BF16) launch_res3_s<SchemeB1>(a, B, C, K, 0, s);
+  else launch_res3_s<SchemeX6>(a, B, C, K, 0, s);
   TTS_HIP_CHECK(hipGetLastError());
 }
 

@@ -55,11 +55,22 @@ constexpr int rb2_halo(int K) { return K == 3 ? 4 : (K == 5 ? 12 : (K == 7 ? 9 :
 // 88,320 B of the padded 80-byte rows, so two workgroups share a CU and drift out of phase: one
 // runs MFMAs while the other sits in its prologue, epilogue or barriers.
 // Measured (f16x3, per batch): C = 128 GEO 4 4.28 ms vs GEO 3 4.73 ms, bitwise the same output
-// (profiles/ab_block_c128_2wg.txt; earlier, GEO 3 5.0 ms vs GEO 2 5.5 ms); 8-wave forms at C = 64
-// (256 columns) and C = 32 (512 columns) were slower than GEO 2 / GEO 0 (+0.2 / +0.3 ms).
+// (profiles/ab_block_c128_2wg.txt; earlier, GEO 3 5.0 ms vs GEO 2 5.5 ms); 8-wave forms on the
+// padded rows at C = 64 (256 columns, 85 KB: one workgroup per CU) and C = 32 (512 columns) were
+// slower than GEO 2 / GEO 0 (+0.2 / +0.3 ms); the 4-wave 256-column form at C = 64 on swizzled rows
+// (SW below, two workgroups per CU) is faster than GEO 2: 2.37 -> 2.26 ms per launch with the
+// upsampling tail (profiles/ab_geo64_wide.txt).
+// SW (C = 64, the two-piece scheme): GEO 0's tile (256 columns, 4 waves side by side, each 64 rows x
+// 64 columns) on the swizzled rows, with everything GEO 4 does for its 64 x 64 wave tile: 4 x 266
+// x 64 = 68,096 B where the padded rows take 85,120 B, so two workgroups share a CU, and 24 of 256
+// columns are halo where the 128-column GEO 2 has 24 of 128.
 // UP: the upsampling tail (ResBlock3Args::up_w), one more bias row in LDS
-template <class S, int C, int GEO, int K = 3, int NCV = 6, int XO = R3_XOFF, int LEAD = R3_LEAD, bool UP = false>
+template <class S, int C, int GEO, int K = 3, int NCV = 6, int XO = R3_XOFF, int LEAD = R3_LEAD, bool UP = false,
+          bool SW = false>
 struct Res3Cfg {
+  static_assert(!SW || (GEO == 0 && S::NP == 2), "SW: GEO 0's tile, two-piece rows");
+  static constexpr bool SWZ = (GEO == 4 || SW) && S::NP == 2;  // swizzled 64-byte rows
+  static constexpr bool W64 = GEO == 4 || SW;                  // a wave owns 64 rows x 64 columns
   static constexpr int RP_W = GEO == 0 ? 256 : (GEO == 1 ? 192 : 128);
   static constexpr int RP_BN = RP_W - 2 * LEAD;
   static constexpr int NW = GEO == 3 ? 8 : 4;     // waves per workgroup
@@ -73,12 +84,12 @@ struct Res3Cfg {
   // row pitch and the place of a 16-byte unit inside a row: every LDS address of the kernel's
   // staged operands is ROWS::off(row, unit), unit = half + 2 piece (+ 8 bytes for the second
   // channel quad of a unit in the prologue's 8-byte stores)
-  using ROWS = Res3Rows<S::NP, GEO == 4 && S::NP == 2>;
-  static_assert(GEO == 4 || ROWS::PITCH == S::ROWB, "the padded layout is the scheme's own row");
+  using ROWS = Res3Rows<S::NP, SWZ>;
+  static_assert(SWZ || ROWS::PITCH == S::ROWB, "the padded layout is the scheme's own row");
   static constexpr int LDSB = NC * PR * ROWS::PITCH;
   // with red and bsm: what a workgroup takes of the CU's 160 KB
   static constexpr int LDS_TOTAL = LDSB + 2 * NW * 4 + (NCV + UP) * C * 4;
-  static_assert(GEO != 4 || LDS_TOTAL <= 80 * 1024, "GEO 4: two workgroups per CU");
+  static_assert(!W64 || LDS_TOTAL <= 80 * 1024, "GEO 4 / SW: two workgroups per CU");
   static_assert(TM >= 1 && TM * WM * 32 == C && TN * WN * 32 == RP_W, "geometry");
 };
 
@@ -89,15 +100,15 @@ struct Res3Cfg {
 #define RB3_W64 2  // A/B build option: waves per SIMD requested for the 64-channel 128-column block
 #endif
 // PL: ResBlock3Args::planes (the bf16 scheme: 0, or bf16 x and z planes; x stays fp32 in registers)
-template <class S, int C, int GEO, int K, int NCV, int XO, int LEAD, int PL = 0, bool UP = false>
+template <class S, int C, int GEO, int K, int NCV, int XO, int LEAD, int PL = 0, bool UP = false, bool SW = false>
 __global__ __launch_bounds__((Res3Cfg<S, C, GEO, K, NCV, XO, LEAD>::NT))
 __attribute__((amdgpu_waves_per_eu(S::NP == 1 && RB3_W_B1 > 0 ? RB3_W_B1
-                                                                : (C == 64 && GEO == 2 ? RB3_W64 : (C == 32 || GEO >= 3 ? 2 : 1)))))
+                                                                : (C == 64 && GEO == 2 ? RB3_W64 : (C == 32 || GEO >= 3 || SW ? 2 : 1)))))
 void resblock3_kernel(ResBlock3Args a) {
   constexpr bool XB = (PL & kPlaneXB16) != 0, YB = (PL & kPlaneYB16) != 0;
   using PX = PlaneT<XB>;
   using PY = PlaneT<YB>;
-  using P = Res3Cfg<S, C, GEO, K, NCV, XO, LEAD, UP>;
+  using P = Res3Cfg<S, C, GEO, K, NCV, XO, LEAD, UP, SW>;
   using ROWS = typename P::ROWS;
   static_assert(NCV == 6 || NCV == 2, "ResBlock1 (6 convs) or ResBlock2 (2 convs)");
   static_assert(!UP || (NCV == 6 && S::SCALED && PL == 0), "the upsampling tail: ResBlock1, f16x3, fp32 planes");
@@ -130,10 +141,10 @@ void resblock3_kernel(ResBlock3Args a) {
     if constexpr (XB) return PX::ld(rx, off, soff);
     else return bload_x<decltype(pol_tag)::value>(rx, off, soff);
   };
-  // GEO 4 (256 registers for a 64 x 64 wave tile) addresses the accumulator layout's 16 channels
+  // GEO 4 / SW (256 registers for a 64 x 64 wave tile) addresses the accumulator layout's 16 channels
   // of a lane as one per-lane offset (column and the lane's half) plus a wave-uniform scalar
   // offset per channel, instead of 16 per-lane offsets for each of the wave's TM x TN blocks
-  constexpr bool SOFF = GEO == 4;
+  constexpr bool SOFF = P::W64;
 
   // ---- prologue: lrelu(x0) pieces for columns [-XO, RP_W + XO) of every 16-channel group, and x0
   // itself in the acc layout.  Every load is issued before the first store (one HBM latency for
@@ -466,7 +477,8 @@ void resblock3_kernel(ResBlock3Args a) {
       for (int n = 0; n < TN; ++n) {
         const int col = xcol0 + n * 32;
         const int t = tx0 + col;
-        const bool tok = t >= 0 && t < T;
+        // only the valid columns are staged below (the rest become zeros), so only they are gathered
+        const bool tok = t >= 0 && t < T && col >= lo && col < hi;
         const unsigned vlane = tok ? (unsigned)(4 * half) * chb + (unsigned)t * 4u : OOB_OFF;
         // the other branches' values, one accumulator block at a time: 32 registers, where the
         // gathers of every block at once would not fit beside acc and x (GEO 4: 128 of 256)
@@ -605,7 +617,7 @@ void resblock3_kernel(ResBlock3Args a) {
       else if constexpr (UP) final_up(2 * it + 1);
       else final_to_z(2 * it + 1);
     };
-    if constexpr (GEO == 4 || UP) {
+    if constexpr (P::W64 || UP) {
       // the 256-register form peels the last iteration: with the z epilogue inside the loop body
       // the compiler carries the residual x in two register sets and spills one block of it
 #pragma unroll 1
