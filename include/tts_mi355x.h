@@ -927,6 +927,98 @@ int tts_op_lstm_cell(const float* d_x, const float* d_h, const float* d_c, int B
                      const float* h_w_hh, const float* h_b_ih, const float* h_b_hh, int math_mode, float* d_h_out,
                      float* d_c_out, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------ */
+/* Conv2d of the SE-ResNet speaker encoder (TTS/encoder/models/resnet.py)                  */
+/* ------------------------------------------------------------------------------------ */
+
+/* One nn.Conv2d with its epilogue, one launch on the matrix cores:
+ *   d_out = scale act(conv2d(d_x, w, stride, padding = (ksize - 1) / 2) + bias) + shift
+ * act = relu (relu != 0) or the identity; scale / shift per output channel: an eval-mode BatchNorm2d
+ * after the ReLU (conv1 / bn1 of the stem and of SEBasicBlock), or bn2 folded by the caller.
+ * d_x [B][Cin][F][T] and d_out [B][Cout][ceil(F / stride)][ceil(T / stride)] on the device, fp32,
+ * not aliased; w [Cout][Cin][ksize][ksize] and bias / scale / shift [Cout] on the host (NULL: 0 / 1 / 0).
+ * ksize 3 (the 3x3 convs) or 1 (the downsample conv); stride 1 or 2; Cout <= 4096; each batch item's
+ * input and output plane below 2 GiB; output rows x ceil(Cout / 256) <= 65535; B <= 65535 (TTS_ERR_UNSUPPORTED
+ * otherwise, before any launch).  math_mode TTS_MATH_FP32_X6 or TTS_MATH_BF16 (TTS_MATH_FP32 and
+ * TTS_MATH_FP32_F16X3 run the fp32x6 kernel: both are held to the fp32 parity gates).  An output
+ * element does not depend on B, and a repeated call returns the same bits. */
+int tts_op_conv2d_3x3(const float* d_x, int B, int Cin, int F, int T, const float* h_w, int Cout, int ksize,
+                      int stride, const float* h_bias, int relu, const float* h_scale, const float* h_shift,
+                      int math_mode, float* d_out, void* hip_stream);
+/* Output columns one workgroup of the conv2d kernel computes (one output row, every channel). */
+int tts_op_conv2d_3x3_tile(void);
+
+/* ------------------------------------------------------------------------------------ */
+/* ResNetSpeakerEncoder (TTS/encoder/models/resnet.py): reference wav -> d-vector          */
+/* ------------------------------------------------------------------------------------ */
+
+#define TTS_SPK_SAP 0
+#define TTS_SPK_ASP 1
+/* Limits of the implemented path (TTS_ERR_UNSUPPORTED beyond, before any launch) */
+#define TTS_SPK_MAX_FILTERS 256   /* num_filters[i]: multiples of 8 in [8, 256] (the SE reduction is C / 8) */
+#define TTS_SPK_MAX_BATCH 4096    /* rows of one forward (compute_embedding's windows count as rows) */
+#define TTS_SPK_MAX_FRAMES 65535  /* frames T of one forward */
+
+/* Mirrors ResNetSpeakerEncoder.__init__: the stem conv1 (1 -> num_filters[0], 3x3, bias) -> ReLU -> bn1,
+ * layers[i] SEBasicBlocks of num_filters[i] channels (stride 2 on the first block of layers 2-4, a
+ * 1x1 downsample conv + BatchNorm wherever the stride or the channel count changes), attentive
+ * pooling (SAP / ASP) over time and the fc projection.  use_torch_spec: the front end (pre-emphasis,
+ * centred STFT with a win_length window, power, mel filterbank) on the device; then fft_size,
+ * win_length and hop_length must satisfy TtsStftCfg's limits.  The log (log_input) and the
+ * instance norm run either way.  Implemented: input_dim a multiple of 8 in [8, 512], num_filters as
+ * above, layers[i] >= 1 with at most 64 blocks in all, proj_dim in [1, 4096].
+ * math_mode: TTS_MATH_BF16 runs the trunk's convs and the two attention convs on bf16 operands;
+ * every other mode runs them fp32x6.  The front end, the SE path, the pooling, fc and the
+ * normalisation are fp32-faithful in every mode. */
+typedef struct TtsSpeakerEncoderCfg {
+  int input_dim;
+  int proj_dim;
+  int layers[4];
+  int num_filters[4];
+  int encoder_type; /* TTS_SPK_SAP or TTS_SPK_ASP */
+  int log_input;
+  int use_torch_spec;
+  int fft_size;   /* torch_spec only */
+  int win_length;
+  int hop_length;
+  int math_mode;
+} TtsSpeakerEncoderCfg;
+
+/* Host weights, fp32, in state_dict order ("BN" = weight, bias, running_mean, running_var):
+ *   use_torch_spec only: torch_spec.0.filter [2], torch_spec.1.spectrogram.window [win_length],
+ *     torch_spec.1.mel_scale.fb [fft_size/2 + 1][input_dim]
+ *   conv1.weight [F0][1][3][3], conv1.bias, bn1 BN
+ *   per block of layer L (C = num_filters[L], Ci its input channels):
+ *     conv1.weight [C][Ci][3][3], bn1 BN, conv2.weight [C][C][3][3], bn2 BN,
+ *     se.fc.0.weight [C/8][C], se.fc.0.bias, se.fc.2.weight [C][C/8], se.fc.2.bias,
+ *     then, where the block has one, downsample.0.weight [C][Ci][1][1], downsample.1 BN
+ *   attention.0.weight [128][D][1] (D = num_filters[3] * input_dim / 8), attention.0.bias, attention.2 BN,
+ *   attention.3.weight [D][128][1], attention.3.bias, fc.weight [proj_dim][D or 2 D], fc.bias */
+int tts_speaker_encoder_num_weights(const TtsSpeakerEncoderCfg* cfg);
+int64_t tts_speaker_encoder_weight_numel(const TtsSpeakerEncoderCfg* cfg, int idx);
+int tts_speaker_encoder_create(const TtsSpeakerEncoderCfg* cfg, const float* const* host_weights, int device,
+                               void** handle);
+int tts_speaker_encoder_destroy(void* handle);
+/* Frames T of an n-sample wav (use_torch_spec: 1 + n / hop_length; else n itself: the input is
+ * features); -TTS_ERR_* when the input is outside the limits (shorter than fft_size/2 + 1 samples, a
+ * row of 2 GiB or more, more than TTS_SPK_MAX_FRAMES frames). */
+int64_t tts_speaker_encoder_num_frames(const void* handle, int64_t n);
+/* d_out[B][proj_dim] = forward(x, l2_norm).  d_x: [B][n] wav samples at the model's sample rate
+ * (use_torch_spec) or [B][input_dim][n] features, contiguous fp32 on the device.  Row b does not
+ * depend on B, and a repeated call returns the same bits.  No host synchronisation. */
+int tts_speaker_encoder_forward(void* handle, const float* d_x, int B, int64_t n, int l2_norm, float* d_out,
+                                void* hip_stream);
+int tts_speaker_encoder_forward_profiled(void* handle, const float* d_x, int B, int64_t n, int l2_norm, float* d_out,
+                                         void* hip_stream, TtsLaunchRecord* records, int max_records, int* n_records);
+/* d_feat[B][input_dim][T]: the trunk's input (front end, log, instance norm) alone, for tests. */
+int tts_speaker_encoder_features(void* handle, const float* d_x, int B, int64_t n, float* d_feat, void* hip_stream);
+
+/* The linear-spectrogram plan of tts_stft_create with torch.stft's frame centring: reflect padding
+ * n_fft / 2, T = 1 + N / hop_length frames (tts_stft_num_frames_centered), N > n_fft / 2.  The handle
+ * is used and destroyed like tts_stft_create's; the output is sqrt(|X|^2 + 1e-6) all the same. */
+int tts_stft_create_centered(const TtsStftCfg* cfg, const float* h_window, int device, void** handle);
+int tts_stft_num_frames_centered(const TtsStftCfg* cfg, int64_t N);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "conv2d.hpp"
 #include "fft_attn.hpp"
 #include "forward_tts.hpp"
 #include "glow.hpp"
@@ -14,6 +15,7 @@
 #include "hifigan.hpp"
 #include "mas.hpp"
 #include "melgan.hpp"
+#include "speaker_encoder.hpp"
 #include "stft.hpp"
 #include "tacotron2.hpp"
 #include "text.hpp"
@@ -1017,6 +1019,98 @@ int tts_op_lstm_cell(const float* d_x, const float* d_h, const float* d_c, int B
     tts::op_lstm_cell(d_x, d_h, d_c, B, I, H, h_w_ih, h_w_hh, h_b_ih, h_b_hh, math_mode, d_h_out, d_c_out,
                       static_cast<hipStream_t>(hip_stream));
   });
+}
+
+int tts_op_conv2d_3x3(const float* d_x, int B, int Cin, int F, int T, const float* h_w, int Cout, int ksize,
+                      int stride, const float* h_bias, int relu, const float* h_scale, const float* h_shift,
+                      int math_mode, float* d_out, void* hip_stream) {
+  return guarded([&] {
+    TTS_REQUIRE(d_x && h_w && d_out, 1, "NULL argument");
+    TTS_REQUIRE(math_mode >= tts::MATH_FP32 && math_mode <= tts::MATH_LAST, 1, "unknown math_mode");
+    const int mode = tts::conv2d_mode(math_mode);
+    tts::Conv2dArgs a{};
+    a.x = d_x; a.y = d_out;
+    a.Cin = Cin; a.Cout = Cout; a.F = F; a.T = T; a.KS = ksize; a.stride = stride; a.relu = relu != 0;
+    tts::conv2d_check(a, B);  // every limit, before anything is packed or launched
+    const int64_t n16 = tts::packed_conv2d_numel16(mode, Cout, Cin, ksize);
+    const size_t nb = (size_t)32 * tts::conv2d_mblocks(Cout);
+    std::vector<float> pa((size_t)n16 / 2), bias(nb), scale(nb), shift(nb);
+    tts::pack_conv2d(mode, h_w, Cout, Cin, ksize, reinterpret_cast<uint16_t*>(pa.data()));
+    tts::pack_conv2d_epilogue(h_bias, h_scale, h_shift, Cout, bias.data(), scale.data(), shift.data());
+    const tts::DeviceBuffer da = to_device(pa.data(), pa.size());
+    const tts::DeviceBuffer db = to_device(bias.data(), nb), dsc = to_device(scale.data(), nb), dsh = to_device(shift.data(), nb);
+    a.a = da.as<>(); a.bias = db.as<>(); a.scale = dsc.as<>(); a.shift = dsh.as<>();
+    a.a_bytes = (unsigned)(n16 * 2);
+    auto s = static_cast<hipStream_t>(hip_stream);
+    tts::launch_conv2d(mode, a, B, s);
+    TTS_HIP_CHECK(hipStreamSynchronize(s));
+  });
+}
+
+int tts_op_conv2d_3x3_tile(void) { return tts::kConv2dTile; }
+
+int tts_speaker_encoder_num_weights(const TtsSpeakerEncoderCfg* cfg) {
+  return num_weights(cfg, tts::speaker_encoder_validate, tts::speaker_encoder_weight_shapes);
+}
+
+int64_t tts_speaker_encoder_weight_numel(const TtsSpeakerEncoderCfg* cfg, int idx) {
+  return weight_numel(cfg, idx, tts::speaker_encoder_validate, tts::speaker_encoder_weight_shapes);
+}
+
+int tts_speaker_encoder_create(const TtsSpeakerEncoderCfg* cfg, const float* const* host_weights, int device,
+                               void** handle) {
+  return create<tts::SpeakerEncoder>(cfg, host_weights, device, handle);
+}
+
+int tts_speaker_encoder_destroy(void* handle) { return destroy<tts::SpeakerEncoder>(handle); }
+
+int64_t tts_speaker_encoder_num_frames(const void* handle, int64_t n) {
+  int64_t T = -1;
+  int st = guarded([&] {
+    TTS_REQUIRE(handle, 1, "NULL handle");
+    T = static_cast<const tts::SpeakerEncoder*>(handle)->num_frames(n);
+  });
+  return st == TTS_OK ? T : -st;
+}
+
+int tts_speaker_encoder_forward(void* handle, const float* d_x, int B, int64_t n, int l2_norm, float* d_out,
+                                void* hip_stream) {
+  return guarded([&] {
+    TTS_REQUIRE(handle, 1, "NULL handle");
+    static_cast<tts::SpeakerEncoder*>(handle)->forward(d_x, B, n, l2_norm, d_out, static_cast<hipStream_t>(hip_stream));
+  });
+}
+
+int tts_speaker_encoder_forward_profiled(void* handle, const float* d_x, int B, int64_t n, int l2_norm, float* d_out,
+                                         void* hip_stream, TtsLaunchRecord* records, int max_records, int* n_records) {
+  auto body = [&](tts::SpeakerEncoder& h, hipStream_t s, tts::Profiler* prof) {
+    h.forward(d_x, B, n, l2_norm, d_out, s, prof);
+  };
+  return profiled<tts::SpeakerEncoder>(handle, hip_stream, records, max_records, n_records, body);
+}
+
+int tts_speaker_encoder_features(void* handle, const float* d_x, int B, int64_t n, float* d_feat, void* hip_stream) {
+  return guarded([&] {
+    TTS_REQUIRE(handle, 1, "NULL handle");
+    static_cast<tts::SpeakerEncoder*>(handle)->features(d_x, B, n, d_feat, static_cast<hipStream_t>(hip_stream));
+  });
+}
+
+int tts_stft_create_centered(const TtsStftCfg* cfg, const float* h_window, int device, void** handle) {
+  return guarded([&] {
+    TTS_REQUIRE(cfg && h_window && handle, 1, "NULL argument");
+    *handle = nullptr;
+    *handle = new tts::Stft(*cfg, h_window, device, /*center=*/true);
+  });
+}
+
+int tts_stft_num_frames_centered(const TtsStftCfg* cfg, int64_t N) {
+  int n = -1;
+  int st = guarded([&] {
+    TTS_REQUIRE(cfg, 1, "NULL cfg");
+    n = tts::stft_num_frames(*cfg, N, /*center=*/true);
+  });
+  return st == TTS_OK ? n : -st;
 }
 
 }  // extern "C"

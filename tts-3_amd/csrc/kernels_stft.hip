@@ -109,6 +109,7 @@ __global__ __launch_bounds__(512) void stft_kernel(StftArgs a) {
   const unsigned avoff = (unsigned)lane * 16u;
   const float sc = H3 ? ldexpf(1.f, ex + a.w_exp) : 1.f;
   const int T = a.T;
+  const bool pw = a.power != 0;  // |X|^2 instead of the magnitude
   const int nh = a.n_fft >> 1;
   const rsrc_t ry = make_rsrc(a.spec + (size_t)b * ((size_t)(nh + 1) * T), (unsigned)(nh + 1) * (unsigned)T * 4u);
 
@@ -205,10 +206,10 @@ __global__ __launch_bounds__(512) void stft_kernel(StftArgs a) {
         }
         float m2 = x * x + y * y;
         if (r == 0 && bin == 0) {  // DC: X[0] in re, the Nyquist bin's X[n_fft/2] in the im slot
-          bstore(ry, sqrtf(y * y + 1e-6f), okc ? ((unsigned)nh * (unsigned)T + (unsigned)t) * 4u : OOB_OFF, 0u);
+          bstore(ry, pw ? y * y : sqrtf(y * y + 1e-6f), okc ? ((unsigned)nh * (unsigned)T + (unsigned)t) * 4u : OOB_OFF, 0u);
           m2 = x * x;
         }
-        bstore(ry, sqrtf(m2 + 1e-6f), okc && bin < nh ? ((unsigned)bin * (unsigned)T + (unsigned)t) * 4u : OOB_OFF, 0u);
+        bstore(ry, pw ? m2 : sqrtf(m2 + 1e-6f), okc && bin < nh ? ((unsigned)bin * (unsigned)T + (unsigned)t) * 4u : OOB_OFF, 0u);
       }
     }
   }

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "conv2d.hpp"
 #include "melgan.hpp"
 #include "stft.hpp"
 #include "tacotron2.hpp"
@@ -312,6 +313,34 @@ void pack_melgan_block(int mode, const float* w1, const float* b1, const float* 
   for (int r = 0; r < 32 * MB; ++r) {
     bias1[r] = r < C ? b1[r] : 0.f;
     bias2[r] = r < C ? b2[r] + bs[r] : 0.f;
+  }
+}
+
+// ---- Conv2d 3x3 / 1x1 (conv2d.hpp): step (g KS + kf) KS + kt, 32-row blocks, the MelGAN fragment order ----
+int conv2d_pieces(int mode) { return split_pieces(conv2d_mode(mode)); }
+
+int64_t packed_conv2d_numel16(int mode, int Cout, int Cin, int KS) {
+  return (int64_t)conv2d_mblocks(Cout) * KS * KS * conv2d_groups(Cin) * conv2d_pieces(mode) * 512;
+}
+
+void pack_conv2d(int mode, const float* w, int Cout, int Cin, int KS, uint16_t* out) {
+  TTS_REQUIRE(mode == MATH_FP32_X6 || mode == MATH_BF16, 3, "conv2d: math mode must be fp32x6 or bf16");
+  TTS_REQUIRE(KS == 3 || KS == 1, 3, "conv2d: the kernel must be 3x3 (pad 1) or 1x1 (pad 0)");
+  TTS_REQUIRE(Cout >= 1 && Cout <= kConv2dMaxCout, 3, "conv2d: output channels must lie in [1, 4096]");
+  TTS_REQUIRE(Cin >= 1 && w && out, 1, "conv2d: bad weights");
+  const int KK = KS * KS;
+  pack_melgan_a(mode, conv2d_mblocks(Cout), KK * conv2d_groups(Cin), out, [&](int row, int col) {
+    const int s = col / 16, g = s / KK, k = s % KK, ci = 16 * g + col % 16;
+    return (row < Cout && ci < Cin) ? w[((int64_t)row * Cin + ci) * KK + k] : 0.f;
+  });
+}
+
+void pack_conv2d_epilogue(const float* bias, const float* scale, const float* shift, int Cout, float* bias_p,
+                          float* scale_p, float* shift_p) {
+  for (int r = 0; r < 32 * conv2d_mblocks(Cout); ++r) {
+    bias_p[r] = (bias && r < Cout) ? bias[r] : 0.f;
+    scale_p[r] = (scale && r < Cout) ? scale[r] : 1.f;
+    shift_p[r] = (shift && r < Cout) ? shift[r] : 0.f;
   }
 }
 

@@ -21,18 +21,22 @@ void stft_validate(const TtsStftCfg& c) {
               "stft: no TTS_MATH_FP32 kernel; use TTS_MATH_FP32_X6 (fp32-exact products) or TTS_MATH_FP32_F16X3");
 }
 
-int stft_num_frames(const TtsStftCfg& c, int64_t N) {
+int stft_pad(const TtsStftCfg& c, bool center) { return center ? c.n_fft / 2 : (c.n_fft - c.hop_length) / 2; }
+
+int stft_num_frames(const TtsStftCfg& c, int64_t N, bool center) {
   stft_validate(c);
-  const int64_t p = (c.n_fft - c.hop_length) / 2;
+  const int64_t p = stft_pad(c, center);
+  if (center) TTS_REQUIRE(N > p, 1, "stft: the wav must be longer than the reflect padding n_fft / 2");
   TTS_REQUIRE(N > p, 1, "stft: the wav must be longer than the reflect padding (n_fft - hop_length) / 2");
   TTS_REQUIRE(N + 2 * p >= c.n_fft, 1, "stft: the padded wav is shorter than one frame");
   TTS_REQUIRE(N * 4 < (int64_t)1 << 31, 3, "stft: a wav row must stay below 2 GiB");
-  const int64_t T = 1 + (N + 2 * p - c.n_fft) / c.hop_length;
+  const int64_t T = 1 + (N + 2 * p - c.n_fft) / c.hop_length;  // center: 1 + N / hop
   TTS_REQUIRE((int64_t)(c.n_fft / 2 + 1) * T * 4 < (int64_t)1 << 31, 3, "stft: a spectrogram must stay below 2 GiB");
   return (int)T;
 }
 
-Stft::Stft(const TtsStftCfg& cfg, const float* h_window, int device) : cfg_(cfg), device_(device) {
+Stft::Stft(const TtsStftCfg& cfg, const float* h_window, int device, bool center, bool power)
+    : cfg_(cfg), device_(device), center_(center), power_(power) {
   stft_validate(cfg);
   std::vector<uint16_t> packed((size_t)packed_stft_numel16(cfg.math_mode, cfg.n_fft));
   w_exp_ = pack_stft_matrix(cfg.math_mode, h_window, cfg.win_length, cfg.n_fft, packed.data());
@@ -45,7 +49,7 @@ void Stft::forward(const float* wav, int B, int64_t N, int64_t wav_bstride, floa
                    Profiler* prof) {
   TTS_REQUIRE(wav && spec, 1, "stft: NULL argument");
   TTS_REQUIRE(B >= 1 && B <= 65535, 1, "stft: batch size must lie in [1, 65535]");
-  const int T = stft_num_frames(cfg_, N);
+  const int T = stft_num_frames(cfg_, N, center_);
   if (wav_bstride == 0) wav_bstride = N;
   TTS_REQUIRE(wav_bstride >= 0, 1, "stft: negative wav_bstride");
   const int mode = cfg_.math_mode;
@@ -63,7 +67,8 @@ void Stft::forward(const float* wav, int B, int64_t N, int64_t wav_bstride, floa
   a.T = T;
   a.n_fft = n_fft;
   a.hop = hop;
-  a.pad = (n_fft - hop) / 2;
+  a.pad = stft_pad(cfg_, center_);
+  a.power = power_ ? 1 : 0;
   a.nblk = stft_blocks(n_fft);
   a.nsteps = n_fft / 16;
   a.w_exp = w_exp_;

@@ -30,7 +30,10 @@ double stft_matrix_entry(const float* window, int win_length, int n_fft, int c, 
 int pack_stft_matrix(int mode, const float* window, int win_length, int n_fft, uint16_t* out);
 
 void stft_validate(const TtsStftCfg& c);
-int stft_num_frames(const TtsStftCfg& c, int64_t N);
+// center = false: reflect padding (n_fft - hop) / 2, T = 1 + (N + 2 pad - n_fft) / hop (VITS);
+// center = true: reflect padding n_fft / 2, T = 1 + N / hop (torch.stft / torchaudio at their defaults)
+int stft_pad(const TtsStftCfg& c, bool center);
+int stft_num_frames(const TtsStftCfg& c, int64_t N, bool center = false);
 
 struct StftArgs {
   const float* wav;      // [B] rows of N samples, wav_bstride floats apart
@@ -39,7 +42,8 @@ struct StftArgs {
   const unsigned* amax;  // [B][64] max-abs slots of the wav (f16x3), or nullptr
   int64_t wav_bstride;
   unsigned a_bytes;
-  int N, T, n_fft, hop, pad;  // pad = (n_fft - hop) / 2
+  int N, T, n_fft, hop, pad;  // pad = stft_pad()
+  int power;                  // 0: sqrt(|X|^2 + 1e-6) (wav_to_spec), 1: |X|^2 (torchaudio power = 2)
   int nblk, nsteps;           // 32-bin blocks, 16-sample k-steps
   int bn;                     // frames per workgroup (<= 32 TN)
   int nhb;                    // hop blocks of the LDS window = bn - 1 + ceil(n_fft / hop)
@@ -54,7 +58,9 @@ void launch_stft(int mode, int TN, const StftArgs& a, int B, int tiles, int RS, 
 
 class Stft {
  public:
-  Stft(const TtsStftCfg& cfg, const float* h_window, int device);
+  // center: frame centring (above); power: the spectrogram holds |X|^2 instead of sqrt(|X|^2 + 1e-6)
+  Stft(const TtsStftCfg& cfg, const float* h_window, int device, bool center = false, bool power = false);
+  int num_frames(int64_t N) const { return stft_num_frames(cfg_, N, center_); }
   void forward(const float* wav, int B, int64_t N, int64_t wav_bstride, float* spec, hipStream_t s,
                Profiler* prof = nullptr);
   int device() const { return device_; }
@@ -62,6 +68,7 @@ class Stft {
  private:
   TtsStftCfg cfg_;
   int device_;
+  bool center_ = false, power_ = false;
   DeviceBuffer a_;  // the packed DFT matrix
   int w_exp_ = 0;
   DeviceBuffer slots_;  // f16x3: [B][64] max-abs slots

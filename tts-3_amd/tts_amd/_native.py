@@ -266,6 +266,28 @@ class TtsTacotron2Cfg(Structure):
     ]
 
 
+SPK_SAP, SPK_ASP = 0, 1
+SPK_MAX_FILTERS = 256
+SPK_MAX_BATCH = 4096
+SPK_MAX_FRAMES = 65535
+
+
+class TtsSpeakerEncoderCfg(Structure):
+    _fields_ = [
+        ("input_dim", c_int),
+        ("proj_dim", c_int),
+        ("layers", c_int * 4),
+        ("num_filters", c_int * 4),
+        ("encoder_type", c_int),
+        ("log_input", c_int),
+        ("use_torch_spec", c_int),
+        ("fft_size", c_int),
+        ("win_length", c_int),
+        ("hop_length", c_int),
+        ("math_mode", c_int),
+    ]
+
+
 class TtsLaunchRecord(Structure):
     _fields_ = [("name", c_char * 48), ("flops", c_double), ("bytes", c_double), ("ms", c_float)]
 
@@ -530,6 +552,27 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
          c_void_p, c_void_p],
     ),
+    "tts_op_conv2d_3x3": (
+        c_int,
+        [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
+         c_int, c_void_p, c_void_p],
+    ),
+    "tts_op_conv2d_3x3_tile": (c_int, []),
+    "tts_speaker_encoder_num_weights": (c_int, [POINTER(TtsSpeakerEncoderCfg)]),
+    "tts_speaker_encoder_weight_numel": (c_int64, [POINTER(TtsSpeakerEncoderCfg), c_int]),
+    "tts_speaker_encoder_create": (
+        c_int, [POINTER(TtsSpeakerEncoderCfg), POINTER(c_void_p), c_int, POINTER(c_void_p)]
+    ),
+    "tts_speaker_encoder_destroy": (c_int, [c_void_p]),
+    "tts_speaker_encoder_num_frames": (c_int64, [c_void_p, c_int64]),
+    "tts_speaker_encoder_forward": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p]),
+    "tts_speaker_encoder_forward_profiled": (
+        c_int,
+        [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, POINTER(TtsLaunchRecord), c_int, POINTER(c_int)],
+    ),
+    "tts_speaker_encoder_features": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
+    "tts_stft_create_centered": (c_int, [POINTER(TtsStftCfg), c_void_p, c_int, POINTER(c_void_p)]),
+    "tts_stft_num_frames_centered": (c_int, [POINTER(TtsStftCfg), c_int64]),
 }
 
 _lib = None

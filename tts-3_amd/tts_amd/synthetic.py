@@ -765,6 +765,76 @@ def tacotron2_state_dict(args, seed: int = 2024) -> "OrderedDict[str, torch.Tens
     return sd
 
 
+def speaker_encoder_state_dict(input_dim=64, proj_dim=512, layers=(3, 4, 6, 3), num_filters=(32, 64, 128, 256),
+                               encoder_type="ASP", use_torch_spec=False, audio_config=None,
+                               seed: int = 2024) -> "OrderedDict[str, torch.Tensor]":
+    """State dict of ``ResNetSpeakerEncoder`` with the reference's keys.  Conv weights N(0, 2 / fan_in),
+    linear (and 1x1 attention conv) weights N(0, 1 / in); BatchNorm gain and running variance
+    U(0.8, 1.2), shift, running mean and every bias 0.1 N(0, 1); the gain and shift of every block's
+    ``bn2`` times 0.5: without it the 16 residual blocks compound to |x| ~ 160 and torch's own fp32
+    forward leaves the fp32 parity gates (3.3e-4 max|d| against fp64)."""
+    rng = np.random.default_rng(seed)
+    sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+
+    def t(v):
+        return torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32))
+
+    def conv(name, cout, cin, k, bias=False):
+        sd[name + ".weight"] = t(rng.standard_normal((cout, cin, k, k)) * np.sqrt(2.0 / (cin * k * k)))
+        if bias:
+            sd[name + ".bias"] = t(0.1 * rng.standard_normal(cout))
+
+    def lin(name, out, inp, shape=None):
+        sd[name + ".weight"] = t(rng.standard_normal(shape or (out, inp)) * np.sqrt(1.0 / inp))
+        sd[name + ".bias"] = t(0.1 * rng.standard_normal(out))
+
+    def bn(name, n, gain=1.0):
+        sd[name + ".weight"] = t(gain * (0.8 + 0.4 * rng.random(n)))
+        sd[name + ".bias"] = t(gain * 0.1 * rng.standard_normal(n))
+        sd[name + ".running_mean"] = t(0.1 * rng.standard_normal(n))
+        sd[name + ".running_var"] = t(0.8 + 0.4 * rng.random(n))
+        sd[name + ".num_batches_tracked"] = torch.tensor(1000, dtype=torch.int64)
+
+    conv("conv1", num_filters[0], 1, 3, bias=True)
+    bn("bn1", num_filters[0])
+    cin = num_filters[0]
+    for li in range(4):
+        C = num_filters[li]
+        for i in range(layers[li]):
+            p = f"layer{li + 1}.{i}"
+            conv(p + ".conv1", C, cin, 3)
+            bn(p + ".bn1", C)
+            conv(p + ".conv2", C, C, 3)
+            bn(p + ".bn2", C, gain=0.5)
+            lin(p + ".se.fc.0", C // 8, C)
+            lin(p + ".se.fc.2", C, C // 8)
+            if (li > 0 and i == 0) or cin != C:
+                conv(p + ".downsample.0", C, cin, 1)
+                bn(p + ".downsample.1", C)
+            cin = C
+    if use_torch_spec:
+        from .encoder.resnet import mel_filterbank
+
+        ac = audio_config
+        sd["torch_spec.0.filter"] = torch.tensor([[[-ac["preemphasis"], 1.0]]], dtype=torch.float32)
+        sd["torch_spec.1.spectrogram.window"] = torch.hamming_window(ac["win_length"])
+        sd["torch_spec.1.mel_scale.fb"] = mel_filterbank(ac["fft_size"] // 2 + 1, ac["sample_rate"], ac["num_mels"]).float()
+    D = num_filters[3] * (input_dim // 8)
+    lin("attention.0", 128, D, shape=(128, D, 1))
+    bn("attention.2", 128)
+    lin("attention.3", D, 128, shape=(D, 128, 1))
+    lin("fc", proj_dim, D if encoder_type == "SAP" else 2 * D)
+    return sd
+
+
+def speaker_wav(batch: int, samples: int, sample_rate: int = 16000, seed: int = 0) -> torch.Tensor:
+    """Synthetic reference audio [B, samples]: clamp(0.25 N(0, 1) + 0.2 sin(2 pi 440 t) + 0.3 sin(2 pi 70 t), -1, 1)."""
+    g = torch.Generator().manual_seed(seed)
+    tt = torch.arange(samples, dtype=torch.float64) / sample_rate
+    tone = 0.2 * torch.sin(2 * np.pi * 440.0 * tt) + 0.3 * torch.sin(2 * np.pi * 70.0 * tt)
+    return (0.25 * torch.randn(batch, samples, generator=g).double() + tone).clamp(-1.0, 1.0).float()
+
+
 def tokens(batch: int, length: int, num_chars: int, seed: int = 0) -> torch.Tensor:
     """Synthetic token ids [B, T] uniform in [0, num_chars) (int64, CPU)."""
     g = torch.Generator().manual_seed(seed)

@@ -5,8 +5,9 @@ on the MI355X path.
 output_hop_length, then x output_sample_rate / input_sample_rate, both ``F.interpolate(mode="linear")``
 with the scale factor as given) run by ``tts_mel_handoff`` with ``src_scale = 1 / scale_factor``,
 then the XTTS ``HifiganGenerator`` (``cond_in_each_up_layer``: ``o = ups[i](o) + conds[i](g)``,
-:276-279) run by ``tts_hifigan_forward``.  The speaker encoder (``ResNetSpeakerEncoder``, used only
-to compute ``g`` from reference audio) is outside the hot path: ``g`` is an input.
+:276-279) run by ``tts_hifigan_forward``.  ``g`` is an input; ``with_speaker_encoder=True`` also builds the
+``ResNetSpeakerEncoder`` (``tts_amd.encoder``) that computes it from 16 kHz reference audio
+(``speaker_embedding``), with the checkpoint's ``speaker_encoder.*`` weights.
 """
 from __future__ import annotations
 
@@ -37,8 +38,15 @@ class HifiDecoder(nn.Module):
         cond_d_vector_in_each_upsampling_layer=True,
         speaker_encoder_audio_config=None,
         math_mode: Optional[str] = None,
+        with_speaker_encoder: bool = False,
     ):
         super().__init__()
+        if with_speaker_encoder:  # opt-in: the default module tree has no speaker_encoder.* keys
+            from ..encoder import XTTS_AUDIO_CONFIG, ResNetSpeakerEncoder
+
+            self.speaker_encoder = ResNetSpeakerEncoder(
+                input_dim=64, proj_dim=512, log_input=True, use_torch_spec=True,
+                audio_config=dict(speaker_encoder_audio_config or XTTS_AUDIO_CONFIG), math_mode=math_mode)
         self.input_sample_rate = input_sample_rate
         self.output_sample_rate = output_sample_rate
         self.output_hop_length = output_hop_length
@@ -74,11 +82,24 @@ class HifiDecoder(nn.Module):
     def inference(self, c: torch.Tensor, g: torch.Tensor) -> torch.Tensor:  # :702-717
         return self.forward(c, g=g)
 
-    def load_checkpoint(self, checkpoint_path, eval=False):  # :719-735 (speaker_encoder keys dropped)
-        state = torch.load(checkpoint_path, map_location="cpu", weights_only=True)
-        state = state["model"] if "model" in state else state
-        state = {k[len("waveform_decoder."):]: v for k, v in state.items() if k.startswith("waveform_decoder.")}
+    @torch.no_grad()
+    def speaker_embedding(self, wav_16k: torch.Tensor) -> torch.Tensor:
+        """wav [B, samples] at 16 kHz (a device tensor) -> g [B, d_vector_dim, 1], as
+        ``Xtts.get_speaker_embedding`` after its resample; needs ``with_speaker_encoder=True``."""
+        if getattr(self, "speaker_encoder", None) is None:
+            raise RuntimeError("this HifiDecoder was built without its speaker encoder: pass with_speaker_encoder=True")
+        return self.speaker_encoder.forward(wav_16k, l2_norm=True).unsqueeze(-1)
+
+    def load_checkpoint(self, checkpoint_path, eval=False):  # :719-735
+        """The ``speaker_encoder.*`` keys are dropped unless the module was built with its speaker
+        encoder; then they are loaded into it."""
+        full = torch.load(checkpoint_path, map_location="cpu", weights_only=True)
+        full = full["model"] if "model" in full else full
+        state = {k[len("waveform_decoder."):]: v for k, v in full.items() if k.startswith("waveform_decoder.")}
         self.waveform_decoder.load_state_dict(state)
+        if getattr(self, "speaker_encoder", None) is not None:
+            pre = "speaker_encoder."
+            self.speaker_encoder.load_state_dict({k[len(pre):]: v for k, v in full.items() if k.startswith(pre)})
         if eval:
             self.eval()
             self.waveform_decoder.remove_weight_norm()
