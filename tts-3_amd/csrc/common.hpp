@@ -157,9 +157,16 @@ bool resblock3_up_supported(int mode, int C, int K, const int* dil, int wide64);
 // (the kernel-3 block keeps 232 columns per workgroup instead of 104, a pair 256 - (K - 1) instead
 // of 192 - (K - 1)); 0: the narrow tiles
 constexpr int kWide64Block = 1, kWide64Pair = 2;
+// wide32 (mrf_geo32_wide), a further bit of the same argument: f16x3 at 32 channels takes 512-column
+// tiles on the swizzled rows for the kernel-7 / 11 whole blocks (440 / 392 kept columns per workgroup
+// instead of 184 / 136), and an executor runs a kernel-7 branch that a later branch follows as one
+// such block instead of three pair launches
+constexpr int kWide32Block = 4;
 void launch_resblock3(int mode, const ResBlock3Args& a, int B, int C, int K, int wide64, hipStream_t s);
 // both bits for f16x3 unless TTS_MI355X_GEO64_WIDE=0; read when an executor is created
 int mrf_geo64_wide(int mode);
+// kWide32Block for f16x3 unless TTS_MI355X_GEO32_WIDE=0; read when an executor is created
+int mrf_geo32_wide(int mode);
 // A whole ResBlock2 (hifigan_generator.py:150-155: two convs of kernel K, dilations dil[0..1],
 // each x = conv(lrelu(x)) + x) in one kernel; ResBlock3Args with w / bias / w_exp[0..1].
 // geo64 = 1: 192-column tiles at C = 64 (default 128)

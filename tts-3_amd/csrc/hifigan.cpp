@@ -113,6 +113,7 @@ Hifigan::Hifigan(const TtsHifiganCfg& cfg, const float* const* hw, int device)
   n_lanes_ = sb ? std::max(1, std::min(std::atoi(sb), 8)) : 2;
   rb2_geo64_ = resblock2_geo64(mode);
   geo64_wide_ = mrf_geo64_wide(mode);
+  geo32_wide_ = mrf_geo32_wide(mode);
   // bf16 planes: every MRF stage length is then a multiple of 8 (the Winograd DMA's 16-byte rows)
   const char* bp = std::getenv("TTS_MI355X_BF16_PLANES");
   planes16_ = mode == MATH_BF16 && !(bp && bp[0] == '0') && cfg_.num_upsamples >= 1 &&
@@ -225,7 +226,11 @@ Hifigan::Hifigan(const TtsHifiganCfg& cfg, const float* const* hw, int device)
           const char* e = std::getenv("TTS_MI355X_RB1_WHOLE_K");
           return std::string(e ? e : "");
         }();
-        const bool k_ok = k == 3 || wk.find(std::to_string(k)) != std::string::npos;
+        // f16x3 at 32 channels (mrf_geo32_wide): a kernel-7 branch that a later branch follows runs
+        // as one whole block on the 512-column tile (about 3.2 plane passes instead of 9.6).  The
+        // stage's last MRF writer keeps the pairs: conv_post lives in the last pair's epilogue
+        const bool k7_block = k == 7 && ch == 32 && (geo32_wide_ & kWide32Block) != 0 && j + 1 < cfg_.num_kernels;
+        const bool k_ok = k == 3 || k7_block || wk.find(std::to_string(k)) != std::string::npos;
         if (cfg_.resblock_type == 1)
           rb.fused3 = ch <= policy && k_ok && resblock3_supported(mode, ch, k, cfg_.resblock_dilation_sizes[j]);
         else
@@ -716,7 +721,8 @@ void Hifigan::forward_plain(const float* mel, int B, int C, int T, int pad, cons
                              4.0 * 6.0 * L1.Cout * L1.Cin * L1.K;
         const std::string nm = "mrf_block_k" + std::to_string(L1.K) + "_c" + std::to_string(L1.Cout);
         zorder();
-        run(prof, sj, nm.c_str(), flops, bytes, [&] { launch_resblock3(L1.mode, ra, B, L1.Cout, L1.K, geo64_wide_, sj); });
+        run(prof, sj, nm.c_str(), flops, bytes,
+            [&] { launch_resblock3(L1.mode, ra, B, L1.Cout, L1.K, geo64_wide_ | geo32_wide_, sj); });
         zdone();
       } else if (cfg_.resblock_type == 1 && rb.fused) {
         // x_{m+1} = convs2[m](lrelu(convs1[m](lrelu(x_m)))) + x_m in one launch per m; the

@@ -118,6 +118,7 @@ class Hifigan {
   int hop_ = 1;
   int rb2_geo64_ = 0;         // ResBlock2 at 64 channels: 1 = 192-column tiles (resblock2_geo64)
   int geo64_wide_ = 0;        // f16x3 at 64 channels: the 256-column tiles (mrf_geo64_wide)
+  int geo32_wide_ = 0;        // f16x3 at 32 channels: the 512-column whole blocks (mrf_geo32_wide)
   bool post_fusion_ = true;  // conv_post inside the last MRF launch (TTS_MI355X_POST_FUSION=0: off)
   // MATH_BF16: the Z / O / X / T activation planes hold bf16 (conv_device.hpp PlaneT), halving the
   // bytes every kernel stages, gathers and stores; TTS_MI355X_BF16_PLANES=0 keeps fp32 planes

@@ -646,7 +646,19 @@ void launch_res3_s(const ResBlock3Args& a, int B, int C, int K, int wide64, hipS
   // workgroups per CU (4.28 ms per batch against 4.73 ms for GEO 3, same bits).  bf16 keeps GEO 3,
   // 8 waves of 32 rows x 64 columns, two per SIMD in one workgroup (its 48-byte rows already fit
   // twice; not re-measured).  Kernels 7 / 11 (32 and 64 channels): the 256-column tile keeps
-  // 184 / 136 columns
+  // 184 / 136 columns.
+  // C = 32, f16x3, kernels 7 / 11: the 512-column tile on swizzled rows (Res3Cfg GEO 5: 440 / 392 of
+  // 512 columns kept, two workgroups per CU) unless TTS_MI355X_GEO32_WIDE=0.  One kernel-7 block,
+  // 1.92 ms per launch, replaces three pair launches of 0.82 ms (profiles/ab_geo32_wide.txt); kernel
+  // 3 keeps GEO 0 (the 512-column form did not meet the step-time rule alone,
+  // experiments/r08_block_k3_c32_geo5.patch)
+  if constexpr (std::is_same<S, SchemeH3>::value) {
+    if (C == 32 && (K == 7 || K == 11) && (wide64 & kWide32Block) && a.planes == 0) {
+      if (K == 7) launch_res3_t<S, 32, 5, 7>(a, B, s);
+      else launch_res3_t<S, 32, 5, 11>(a, B, s);
+      return;
+    }
+  }
   if (K == 7) {
     if (C == 32) launch_res3_t<S, 32, 0, 7>(a, B, s);
     else launch_res3_t<S, 64, 0, 7>(a, B, s);
@@ -701,6 +713,12 @@ int mrf_geo64_wide(int mode) {
   // one switch for both parts; each alone was measured with a build that read "block" / "pair"
   // here (profiles/ab_geo64_wide.txt) and both stayed
   return e && e[0] == '0' ? 0 : (kWide64Block | kWide64Pair);
+}
+
+int mrf_geo32_wide(int mode) {
+  if (mode != MATH_FP32_F16X3) return 0;
+  const char* e = std::getenv("TTS_MI355X_GEO32_WIDE");
+  return e && e[0] == '0' ? 0 : kWide32Block;
 }
 
 bool resblock3_up_supported(int mode, int C, int K, const int* dil, int wide64) {

@@ -93,6 +93,36 @@ struct Res3Cfg {
   static_assert(TM >= 1 && TM * WM * 32 == C && TN * WN * 32 == RP_W, "geometry");
 };
 
+// GEO 5 (C = 32, the two-piece scheme, ResBlock1): 512 columns, 4 waves side by side, each 32 rows x
+// 128 columns (TM 1, TN 4), on the swizzled rows with everything GEO 4 / SW do for their 64 x 64 wave
+// tile (W64: operand addresses per (group, tap), scalar-offset residual and z addressing, the last
+// iteration peeled, two waves per SIMD): the same 64 accumulators and 64 residual registers per
+// lane, 64 B operand registers.  2 x (512 + 2 XO) x 64 B of LDS: 66,816 / 69,376 / 71,936 B at kernels
+// 3 / 7 / 11, two workgroups per CU; the kept columns are 488 / 440 / 392 of 512 where GEO 0 keeps
+// 232 / 184 / 136 of 256.  Launched at kernels 7 / 11 (launch_res3_s); the kernel-7 block ran 1.92 ms
+// per launch where three pairs took 2.45 ms (profiles/ab_geo32_wide.txt)
+template <class S, int C, int K, int NCV, int XO, int LEAD, bool UP, bool SW>
+struct Res3Cfg<S, C, 5, K, NCV, XO, LEAD, UP, SW> {
+  static_assert(C == 32 && S::NP == 2 && NCV == 6 && !UP && !SW, "GEO 5: the 32-channel ResBlock1, two-piece rows");
+  static constexpr bool SWZ = true;
+  static constexpr bool W64 = true;  // the 256-register form of the kernel
+  static constexpr int RP_W = 512;
+  static constexpr int RP_BN = RP_W - 2 * LEAD;
+  static constexpr int NW = 4;
+  static constexpr int NT = 64 * NW;
+  static constexpr int WN = 4;
+  static constexpr int WM = 1;
+  static constexpr int TM = 1;
+  static constexpr int TN = RP_W / 32 / WN;
+  static constexpr int NC = C / 16;
+  static constexpr int PR = RP_W + 2 * XO;
+  using ROWS = Res3Rows<S::NP, SWZ>;
+  static constexpr int LDSB = NC * PR * ROWS::PITCH;
+  static constexpr int LDS_TOTAL = LDSB + 2 * NW * 4 + NCV * C * 4;
+  static_assert(LDS_TOTAL <= 80 * 1024, "GEO 5: two workgroups per CU");
+  static_assert(RP_BN > 0 && TN * WN * 32 == RP_W, "geometry");
+};
+
 #ifndef RB3_W_B1
 #define RB3_W_B1 0  // A/B: waves per SIMD asked of the bf16 scheme's whole-block kernels (0: as the others)
 #endif
@@ -141,8 +171,8 @@ void resblock3_kernel(ResBlock3Args a) {
     if constexpr (XB) return PX::ld(rx, off, soff);
     else return bload_x<decltype(pol_tag)::value>(rx, off, soff);
   };
-  // GEO 4 / SW (256 registers for a 64 x 64 wave tile) addresses the accumulator layout's 16 channels
-  // of a lane as one per-lane offset (column and the lane's half) plus a wave-uniform scalar
+  // GEO 4 / SW / GEO 5 (256 registers for a 64 x 64 or 32 x 128 wave tile) address the accumulator
+  // layout's 16 channels of a lane as one per-lane offset (column and the lane's half) plus a wave-uniform scalar
   // offset per channel, instead of 16 per-lane offsets for each of the wave's TM x TN blocks
   constexpr bool SOFF = P::W64;
 
