@@ -185,7 +185,10 @@ def test_op_conv_transpose1d(cuda_device, case, mode):
     assert_close_fp32(y.cpu(), ref, f"convT {case}", **tol(mode, op=True))
 
 
-@pytest.mark.parametrize("B,Cin,T", [(2, 32, 1000), (1, 32, 1), (3, 8, 513), (2, 64, 3001), (1, 20, 1024), (2, 32, 2052), (1, 13, 4)])
+@pytest.mark.parametrize("B,Cin,T", [(2, 32, 1000), (1, 32, 1), (3, 8, 513), (2, 64, 3001), (1, 20, 1024), (2, 32, 2052), (1, 13, 4),
+                                     # around the 1024-column workgroup (POST_T): T % 4 == 0 takes the vector form
+                                     # (conv_post4_kernel), every other length the scalar one
+                                     (2, 32, 1020), (1, 9, 1023), (2, 13, 1025), (1, 64, 1028), (3, 8, 2048), (2, 20, 2049)])
 def test_op_conv_post(cuda_device, B, Cin, T):
     g = _rng(T)
     z = torch.randn(B, Cin, T, generator=g)

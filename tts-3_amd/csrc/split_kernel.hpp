@@ -364,7 +364,8 @@ void launch_split_t(const Conv1dArgs& a, int B, hipStream_t s) {
         } else if (WIDE && halo <= 96) {
           hipLaunchKernelGGL((conv1d_split_kernel<S, K, BM, BN, TM, TN, G, WIDE ? 96 : 0, PD, false, PLc>), grid, dim3(256), 0, s, a);
         } else {
-          throw Error(3, "conv1d(split): (kernel_size-1)*dilation = " + std::to_string(halo) + " too large for this tile");
+          throw Error(3, "conv1d(split): (kernel_size-1)*dilation = " + std::to_string(halo) + " exceeds " +
+                           std::to_string(WIDE ? 96 : (K - 1) * 5) + " for this tile");
         }
       };
       if (a.planes == kPlaneYB16) {
@@ -380,7 +381,8 @@ void launch_split_t(const Conv1dArgs& a, int B, hipStream_t s) {
   } else if (WIDE && halo <= 96) {
     hipLaunchKernelGGL((conv1d_split_kernel<S, K, BM, BN, TM, TN, G, WIDE ? 96 : 0, PD>), grid, dim3(256), 0, s, a);
   } else {
-    throw Error(3, "conv1d(split): (kernel_size-1)*dilation = " + std::to_string(halo) + " too large for this tile");
+    throw Error(3, "conv1d(split): (kernel_size-1)*dilation = " + std::to_string(halo) + " exceeds " +
+                     std::to_string(WIDE ? 96 : (K - 1) * 5) + " for this tile");
   }
 }
 
