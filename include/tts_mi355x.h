@@ -1019,6 +1019,112 @@ int tts_speaker_encoder_features(void* handle, const float* d_x, int B, int64_t 
 int tts_stft_create_centered(const TtsStftCfg* cfg, const float* h_window, int device, void** handle);
 int tts_stft_num_frames_centered(const TtsStftCfg* cfg, int64_t N);
 
+/* ---- XTTS GPT (TTS/tts/layers/xtts/gpt.py, gpt_inference.py: the autoregressive GPT-2 trunk that
+ * turns text tokens and conditioning latents into audio codes and the decoder's latents) ----
+ * A step is a chain of launches on the caller's stream: 5 per layer (c_attn with ln_1 -> q and the
+ * cache row, attention over the cache, c_proj + residual, c_fc with ln_2 + gelu_new, mlp c_proj +
+ * residual) and 2 beyond the layers (ln_f / final_norm / mel_head; logits -> token with the
+ * bookkeeping and the next input).  Steps are enqueued in chunks of `chunk`; after each chunk the
+ * host reads one word and stops when every utterance has ended.  math_mode TTS_MATH_BF16 stores the
+ * layers' matrices and mel_head as bf16 (fp32 accumulation); every other mode keeps fp32 matrices with
+ * exact fp32 FMA products.  The KV cache, the residual stream, LayerNorm and the softmax are fp32 in
+ * every mode.  Utterance b of a batch is bitwise its own batch of one.
+ * Limits (TTS_ERR_UNSUPPORTED, before any launch): B <= TTS_XTTS_GPT_MAX_BATCH, head size
+ * model_dim / heads of 32, 64 or 128, model_dim a multiple of 64, n_audio_tokens <=
+ * TTS_XTTS_GPT_MAX_AUDIO_TOKENS.  A sequence past the position tables is TTS_ERR_INVALID (the
+ * reference's assert). */
+#define TTS_XTTS_GPT_MAX_BATCH 32
+#define TTS_XTTS_GPT_MAX_AUDIO_TOKENS 8194
+typedef struct TtsXttsGptCfg {
+  int layers, model_dim, heads;      /* 30, 1024, 16 */
+  int n_text_tokens, n_audio_tokens; /* rows of text_embedding / mel_embedding (and of mel_head) */
+  int start_text_token, stop_text_token, start_audio_token, stop_audio_token;
+  int text_positions;   /* rows of text_pos_embedding.emb.weight (max_text_tokens + 2) */
+  int mel_positions;    /* rows of mel_pos_embedding.emb.weight */
+  int prompt_positions; /* P: conditioning latent rows in front of every utterance's text */
+  int chunk;            /* steps enqueued between two host reads of the all-done word; 0: 32 */
+  int math_mode;
+} TtsXttsGptCfg;
+
+/* Host weight order, E = model_dim:
+ *   text_embedding.weight [n_text][E]; mel_embedding.weight [n_audio][E];
+ *   text_pos_embedding.emb.weight [text_positions][E]; mel_pos_embedding.emb.weight [mel_positions][E];
+ *   per layer gpt.h.{i}: ln_1.weight, ln_1.bias, attn.c_attn.weight [E][3E], .bias, attn.c_proj.weight
+ *     [E][E], .bias, ln_2.weight, ln_2.bias, mlp.c_fc.weight [E][4E], .bias, mlp.c_proj.weight [4E][E],
+ *     .bias (HF Conv1D: [in][out], y = x W + b, passed as stored);
+ *   gpt.ln_f.weight, .bias; final_norm.weight, .bias; mel_head.weight [n_audio][E], .bias. */
+int tts_xtts_gpt_num_weights(const TtsXttsGptCfg* cfg);
+int64_t tts_xtts_gpt_weight_numel(const TtsXttsGptCfg* cfg, int index);
+int tts_xtts_gpt_create(const TtsXttsGptCfg* cfg, const float* const* host_weights, int device, void** handle);
+int tts_xtts_gpt_destroy(void* handle);
+/* The prefix of utterance b, [cond latents (P rows) | start_text, text_b, stop_text] with the text
+ * position embedding, through the layers into the cache rows [0, P + L_b + 2).  d_cond [B][P][E],
+ * d_tokens [B][T_text] int64, d_text_lengths [B] int64 or NULL (L_b = T_text).  The handle keeps the
+ * prefix (and room for max_new_tokens steps behind it) until the next prefill; tts_xtts_gpt_generate
+ * and tts_xtts_gpt_latents may follow it any number of times.  Token ids outside the table are clamped
+ * (the Python module raises IndexError on the host, as torch's embedding does).  No host
+ * synchronisation.  One whole-sequence pass on the conv path: per layer LayerNorm, c_attn as a 1x1 conv
+ * (fp32x6; in TTS_MATH_BF16 on the bf16-rounded matrix the steps stream, activations stay fp32), K and V
+ * from the planes into the cache layout, causal MFMA
+ * attention (tts_op_mha_causal's kernel), c_proj + residual, LayerNorm, c_fc, gelu_new, mlp c_proj +
+ * residual.  The _profiled form is an extension for the step benchmark. */
+int tts_xtts_gpt_prefill(void* handle, const float* d_cond, const int64_t* d_tokens, const int64_t* d_text_lengths,
+                         int B, int T_text, int max_new_tokens, void* hip_stream);
+int tts_xtts_gpt_prefill_profiled(void* handle, const float* d_cond, const int64_t* d_tokens,
+                                  const int64_t* d_text_lengths, int B, int T_text, int max_new_tokens,
+                                  void* hip_stream, TtsLaunchRecord* records, int max_records, int* n_records);
+/* The step loop.  Step s reads the hidden state of mel position s (the start token at s = 0) and
+ * chooses code s: repetition penalty over {1, start_audio} and the codes so far, then with d_uniforms
+ * [B][max_new_tokens] (in [0, 1)): temperature, top-k (<= 0: off), top-p and a draw by inverse CDF in
+ * token order; with d_uniforms NULL: the argmax after the penalty, the lowest id on ties.  Utterance
+ * b ends at its first stop_audio or after max_new_tokens (<= the prefill's); d_codes [B][max_new_tokens]
+ * int32 holds stop_audio past its end and d_lengths [B] int32 its code count, the stop included.
+ * Optional (NULL: not written), zero past an utterance's end: d_logits [B][max_new_tokens][n_audio],
+ * the logits after mel_head, and d_latents [B][max_new_tokens][E], final_norm(ln_f(h)) of every
+ * step's position.  d_latents is an extension: it holds what the reference's second pass
+ * (tts_xtts_gpt_latents over the generated codes) recomputes, so a caller that passes it can skip that
+ * pass, as Xtts.inference does.  Synchronises the stream once per chunk; *steps_run (host, may be NULL) = steps
+ * enqueued. */
+int tts_xtts_gpt_generate(void* handle, int max_new_tokens, float repetition_penalty, float temperature, int top_k,
+                          float top_p, const float* d_uniforms, int32_t* d_codes, int32_t* d_lengths, float* d_logits,
+                          float* d_latents, int* steps_run, void* hip_stream);
+int tts_xtts_gpt_generate_profiled(void* handle, int max_new_tokens, float repetition_penalty, float temperature,
+                                   int top_k, float top_p, const float* d_uniforms, int32_t* d_codes,
+                                   int32_t* d_lengths, float* d_logits, float* d_latents, int* steps_run,
+                                   void* hip_stream, TtsLaunchRecord* records, int max_records, int* n_records);
+/* The teacher-forced pass over the mel inputs [start_audio, c_0 .. c_{n_b - 1}, stop_audio] of given
+ * codes d_codes [B][S] int32 with d_lengths [B] int32 (n_b), mel positions [0, rows), rows <= the
+ * prefill's max_new_tokens.  d_latents [B][rows][E] (or NULL): final_norm(ln_f(h)), rows at or past
+ * n_b - 2 zero (the reference drops the last 4 of its n_b + 2 positions); d_logits
+ * [B][rows][n_audio] (or NULL), rows at or past n_b + 2 zero.  No host synchronisation.  One
+ * whole-sequence pass over [prefix | mel rows] on the conv path, as the prefill (the prefix from the input
+ * rows the prefill kept), then ln_f / final_norm / mel_head per mel position. */
+int tts_xtts_gpt_latents(void* handle, const int32_t* d_codes, const int32_t* d_lengths, int S, int rows,
+                         float* d_latents, float* d_logits, void* hip_stream);
+int tts_xtts_gpt_latents_profiled(void* handle, const int32_t* d_codes, const int32_t* d_lengths, int S, int rows,
+                                  float* d_latents, float* d_logits, void* hip_stream, TtsLaunchRecord* records,
+                                  int max_records, int* n_records);
+/* Single-query attention over a KV cache, for kernel tests: d_q [B][E], d_k / d_v [B][cap][E],
+ * d_lengths [B] int32 (keys [0, len_b), 1 <= len_b <= cap), d_out [B][E].  A workgroup of
+ * tts_op_gpt_decode_attn_waves() waves per (utterance, head); wave w takes the 64-key tiles w, w + waves,
+ * ... and the waves' partial results are merged in wave order.  Row b does not depend on B. */
+int tts_op_gpt_decode_attn(const float* d_q, const float* d_k, const float* d_v, const int32_t* d_lengths, int B,
+                           int E, int heads, int cap, float* d_out, void* hip_stream);
+int tts_op_gpt_decode_attn_waves(void);
+/* tts_op_mha with a causal mask (the GPT's attention over a whole sequence): query i attends to the
+ * keys j <= i with j < key_lengths[b].  Key tiles wholly above a workgroup's diagonal are skipped, the
+ * diagonal tiles are masked, so the outputs at positions <= i are bitwise independent of everything
+ * at a position > i.  Arguments, layouts and math modes as tts_op_mha (tile: tts_op_mha_tile()); head
+ * sizes 32, 64 or 128 with E <= 2048 (TTS_ERR_UNSUPPORTED otherwise).  It is the attention of the XTTS
+ * GPT's prefill and latent pass. */
+int tts_op_mha_causal(const float* d_qkv, const int64_t* d_key_lengths, int B, int E, int heads, int T,
+                      int math_mode, float* d_out, void* hip_stream);
+/* The logits -> token step alone, for kernel tests: d_logits [B][V], d_codes [B][n_prev + 1] int32
+ * (the earlier codes, then the slot that receives the token), d_uniforms [B] or NULL (greedy). */
+int tts_op_gpt_sample(const float* d_logits, int B, int V, int32_t* d_codes, int n_prev, int start_audio_token,
+                      float repetition_penalty, float temperature, int top_k, float top_p, const float* d_uniforms,
+                      void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

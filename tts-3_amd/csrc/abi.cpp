@@ -20,6 +20,7 @@
 #include "tacotron2.hpp"
 #include "text.hpp"
 #include "vits.hpp"
+#include "xtts_gpt.hpp"
 #include "tts_mi355x.h"
 
 namespace {
@@ -1111,6 +1112,109 @@ int tts_stft_num_frames_centered(const TtsStftCfg* cfg, int64_t N) {
     n = tts::stft_num_frames(*cfg, N, /*center=*/true);
   });
   return st == TTS_OK ? n : -st;
+}
+
+// ----------------------------------------------------------------------------- XTTS GPT
+int tts_xtts_gpt_num_weights(const TtsXttsGptCfg* cfg) {
+  return num_weights(cfg, tts::xtts_gpt_validate, tts::xtts_gpt_weight_shapes);
+}
+
+int64_t tts_xtts_gpt_weight_numel(const TtsXttsGptCfg* cfg, int idx) {
+  return weight_numel(cfg, idx, tts::xtts_gpt_validate, tts::xtts_gpt_weight_shapes);
+}
+
+int tts_xtts_gpt_create(const TtsXttsGptCfg* cfg, const float* const* host_weights, int device, void** handle) {
+  return create<tts::XttsGpt>(cfg, host_weights, device, handle);
+}
+
+int tts_xtts_gpt_destroy(void* handle) { return destroy<tts::XttsGpt>(handle); }
+
+int tts_xtts_gpt_prefill(void* handle, const float* d_cond, const int64_t* d_tokens, const int64_t* d_text_lengths,
+                         int B, int T_text, int max_new_tokens, void* hip_stream) {
+  return guarded([&] {
+    TTS_REQUIRE(handle, 1, "NULL handle");
+    static_cast<tts::XttsGpt*>(handle)->prefill(d_cond, d_tokens, d_text_lengths, B, T_text, max_new_tokens,
+                                                static_cast<hipStream_t>(hip_stream));
+  });
+}
+
+int tts_xtts_gpt_prefill_profiled(void* handle, const float* d_cond, const int64_t* d_tokens,
+                                  const int64_t* d_text_lengths, int B, int T_text, int max_new_tokens,
+                                  void* hip_stream, TtsLaunchRecord* records, int max_records, int* n_records) {
+  auto body = [&](tts::XttsGpt& h, hipStream_t s, tts::Profiler* prof) {
+    h.prefill(d_cond, d_tokens, d_text_lengths, B, T_text, max_new_tokens, s, prof);
+  };
+  return profiled<tts::XttsGpt>(handle, hip_stream, records, max_records, n_records, body);
+}
+
+int tts_xtts_gpt_generate(void* handle, int max_new_tokens, float repetition_penalty, float temperature, int top_k,
+                          float top_p, const float* d_uniforms, int32_t* d_codes, int32_t* d_lengths, float* d_logits,
+                          float* d_latents, int* steps_run, void* hip_stream) {
+  return guarded([&] {
+    TTS_REQUIRE(handle, 1, "NULL handle");
+    const int n = static_cast<tts::XttsGpt*>(handle)->generate(
+        max_new_tokens, repetition_penalty, temperature, top_k, top_p, d_uniforms, d_codes, d_lengths, d_logits,
+        d_latents, static_cast<hipStream_t>(hip_stream));
+    if (steps_run) *steps_run = n;
+  });
+}
+
+int tts_xtts_gpt_generate_profiled(void* handle, int max_new_tokens, float repetition_penalty, float temperature,
+                                   int top_k, float top_p, const float* d_uniforms, int32_t* d_codes,
+                                   int32_t* d_lengths, float* d_logits, float* d_latents, int* steps_run,
+                                   void* hip_stream, TtsLaunchRecord* records, int max_records, int* n_records) {
+  auto body = [&](tts::XttsGpt& h, hipStream_t s, tts::Profiler* prof) {
+    const int n = h.generate(max_new_tokens, repetition_penalty, temperature, top_k, top_p, d_uniforms, d_codes,
+                             d_lengths, d_logits, d_latents, s, prof);
+    if (steps_run) *steps_run = n;
+  };
+  return profiled<tts::XttsGpt>(handle, hip_stream, records, max_records, n_records, body);
+}
+
+int tts_xtts_gpt_latents(void* handle, const int32_t* d_codes, const int32_t* d_lengths, int S, int rows,
+                         float* d_latents, float* d_logits, void* hip_stream) {
+  return guarded([&] {
+    TTS_REQUIRE(handle, 1, "NULL handle");
+    static_cast<tts::XttsGpt*>(handle)->latents(d_codes, d_lengths, S, rows, d_latents, d_logits,
+                                                static_cast<hipStream_t>(hip_stream));
+  });
+}
+
+int tts_xtts_gpt_latents_profiled(void* handle, const int32_t* d_codes, const int32_t* d_lengths, int S, int rows,
+                                  float* d_latents, float* d_logits, void* hip_stream, TtsLaunchRecord* records,
+                                  int max_records, int* n_records) {
+  auto body = [&](tts::XttsGpt& h, hipStream_t s, tts::Profiler* prof) {
+    h.latents(d_codes, d_lengths, S, rows, d_latents, d_logits, s, prof);
+  };
+  return profiled<tts::XttsGpt>(handle, hip_stream, records, max_records, n_records, body);
+}
+
+int tts_op_gpt_decode_attn(const float* d_q, const float* d_k, const float* d_v, const int32_t* d_lengths, int B,
+                           int E, int heads, int cap, float* d_out, void* hip_stream) {
+  return guarded([&] {
+    tts::op_gpt_decode_attn(d_q, d_k, d_v, d_lengths, B, E, heads, cap, d_out, static_cast<hipStream_t>(hip_stream));
+  });
+}
+
+int tts_op_gpt_decode_attn_waves(void) { return tts::kGptAttnWaves; }
+
+int tts_op_mha_causal(const float* d_qkv, const int64_t* d_key_lengths, int B, int E, int heads, int T, int math_mode,
+                      float* d_out, void* hip_stream) {
+  return guarded([&] {
+    TTS_REQUIRE(d_qkv && d_out, 1, "NULL argument");
+    TTS_REQUIRE(math_mode >= tts::MATH_FP32 && math_mode <= tts::MATH_LAST, 1, "unknown math_mode");
+    const int mode = math_mode == tts::MATH_BF16 ? tts::MATH_BF16 : tts::MATH_FP32_X6;
+    tts::launch_mha_causal(mode, d_qkv, d_key_lengths, d_out, B, E, heads, T, static_cast<hipStream_t>(hip_stream));
+  });
+}
+
+int tts_op_gpt_sample(const float* d_logits, int B, int V, int32_t* d_codes, int n_prev, int start_audio_token,
+                      float repetition_penalty, float temperature, int top_k, float top_p, const float* d_uniforms,
+                      void* hip_stream) {
+  return guarded([&] {
+    tts::op_gpt_sample(d_logits, B, V, d_codes, n_prev, start_audio_token, repetition_penalty, temperature, top_k,
+                       top_p, d_uniforms, static_cast<hipStream_t>(hip_stream));
+  });
 }
 
 }  // extern "C"

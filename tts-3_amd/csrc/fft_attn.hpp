@@ -25,5 +25,12 @@ bool mha_head_size_ok(int dk);
 // mode: MATH_FP32_X6 or MATH_BF16.  Results do not depend on B.
 void launch_mha(int mode, const float* qkv, const int64_t* key_len, float* out, int B, int E, int heads, int T,
                 hipStream_t s);
+// The causal variant (the XTTS GPT's attention over a whole sequence): query i attends to the keys
+// j <= i with j < key_len[b].  Key tiles wholly above a workgroup's diagonal are skipped, the diagonal
+// tiles are masked; the outputs at positions <= i do not depend on anything at a position > i.
+// Head sizes 32, 64, 128 with E <= kMhaCausalMaxE; otherwise as launch_mha.
+constexpr int kMhaCausalMaxE = 2048;
+void launch_mha_causal(int mode, const float* qkv, const int64_t* key_len, float* out, int B, int E, int heads, int T,
+                       hipStream_t s);
 
 }  // namespace tts

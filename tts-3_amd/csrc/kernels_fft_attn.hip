@@ -57,7 +57,11 @@ __device__ __forceinline__ void split_frag(const float (&v)[8], f32x4 (&f)[S::NP
   for (int p = 0; p < S::NP; ++p) f[p] = __builtin_bit_cast(f32x4, u32x4_t{w[0][p], w[1][p], w[2][p], w[3][p]});
 }
 
-template <class S, int DK>
+// CAUSAL: query i attends to the keys j <= i only (and j < key_len).  A workgroup stops after the key
+// tile that holds its last query's diagonal (tiles wholly above the diagonal are skipped) and masks
+// the keys above each query's own diagonal like padded keys: their probability is exactly 0, so
+// nothing at a position > i reaches the output of position i.
+template <class S, int DK, bool CAUSAL = false>
 __global__ __launch_bounds__(256) void mha_kernel(MhaArgs a) {
   constexpr int NP = S::NP;
   constexpr int ROWB = S::ROWB;
@@ -149,7 +153,8 @@ __global__ __launch_bounds__(256) void mha_kernel(MhaArgs a) {
     for (int i = 0; i < NU; ++i) kload(0, i, kr[i]);
   }
 
-  for (int k0 = 0; k0 < klen; k0 += KT) {
+  const int kend = CAUSAL ? min(klen, ((int)blockIdx.x + 1) * kMhaTile) : klen;
+  for (int k0 = 0; k0 < kend; k0 += KT) {
     // ---- K tile -> LDS ----
 #pragma unroll
     for (int i = 0; i < NU; ++i) {
@@ -205,11 +210,12 @@ __global__ __launch_bounds__(256) void mha_kernel(MhaArgs a) {
       const float s0 = dh == 0 ? sc[r] : sx[((wave ^ 2) * 16 + r) * 64 + lane];
       const float s1 = dh == 0 ? sx[((wave ^ 2) * 16 + r) * 64 + lane] : sc[r];
       const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * half;
-      sc[r] = key < klen ? s0 + s1 : -INFINITY;
+      sc[r] = (key < klen && (!CAUSAL || key <= qi)) ? s0 + s1 : -INFINITY;
       mt = fmaxf(mt, sc[r]);
     }
     mt = fmaxf(mt, __shfl_xor(mt, 32));
-    // key k0 < klen is in every query's tile: the new maximum is finite
+    // key k0 < klen is in every query's tile: the new maximum is finite (causal: key 0 is in every
+    // query's first tile, and a later tile wholly above a query's diagonal leaves its maximum alone)
     const float m_new = fmaxf(m_run, mt);
     const float alpha = exp2f(m_run - m_new);  // first tile: exp2(-inf) = 0
     m_run = m_new;
@@ -278,11 +284,11 @@ bool mha_head_size_ok(int dk) { return dk == 32 || dk == 64 || dk == 128 || dk =
 namespace {
 constexpr int kMhaLdsLimit = 160 * 1024;
 
-template <class S, int DK>
+template <class S, int DK, bool CAUSAL = false>
 void launch_mha_k(const MhaArgs& a, const dim3& grid, hipStream_t s) {
   constexpr size_t lds = (size_t)2 * DK * S::ROWB + 4 * 16 * 64 * sizeof(float);
   static_assert(lds <= (size_t)kMhaLdsLimit, "the tile does not fit the LDS");
-  auto kernel = mha_kernel<S, DK>;
+  auto kernel = mha_kernel<S, DK, CAUSAL>;
   if (lds > 64 * 1024)
     TTS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)lds));
@@ -300,7 +306,34 @@ void launch_mha_s(int dk, const MhaArgs& a, const dim3& grid, hipStream_t s) {
     default: launch_mha_k<S, 384>(a, grid, s); break;
   }
 }
+
+template <class S>
+void launch_mha_causal_s(int dk, const MhaArgs& a, const dim3& grid, hipStream_t s) {
+  switch (dk) {
+    case 32: launch_mha_k<S, 32, true>(a, grid, s); break;
+    case 64: launch_mha_k<S, 64, true>(a, grid, s); break;
+    default: launch_mha_k<S, 128, true>(a, grid, s); break;
+  }
+}
 }  // namespace
+
+void launch_mha_causal(int mode, const float* qkv, const int64_t* key_len, float* out, int B, int E, int heads, int T,
+                       hipStream_t s) {
+  TTS_REQUIRE(mode == MATH_FP32_X6 || mode == MATH_BF16, 3, "mha: math mode must be fp32x6 or bf16");
+  TTS_REQUIRE(B >= 1 && E >= 1 && heads >= 1 && T >= 1, 1, "mha: bad shape");
+  TTS_REQUIRE(E % heads == 0, 1, "mha: the channels must divide into the heads");
+  const int dk = E / heads;
+  TTS_REQUIRE(E <= kMhaCausalMaxE && (dk == 32 || dk == 64 || dk == 128), 3,
+              "causal mha: head size must be one of 32, 64, 128 with at most 2048 channels");
+  TTS_REQUIRE(B <= 65535 && heads <= 65535, 3, "mha: batch size and heads must lie in [1, 65535]");
+  TTS_REQUIRE((int64_t)3 * E * T * 4 < (int64_t)1 << 31, 3, "mha: a batch item's qkv plane exceeds 2 GiB");
+  TTS_REQUIRE(qkv != out, 1, "mha: the output must not alias the input");
+  MhaArgs a{qkv, key_len, out, E, T, kLog2e / sqrtf((float)dk)};
+  const dim3 grid((T + kMhaTile - 1) / kMhaTile, heads, B);
+  if (mode == MATH_BF16) launch_mha_causal_s<SchemeB1>(dk, a, grid, s);
+  else launch_mha_causal_s<SchemeX6>(dk, a, grid, s);
+  TTS_HIP_CHECK(hipGetLastError());
+}
 
 void launch_mha(int mode, const float* qkv, const int64_t* key_len, float* out, int B, int E, int heads, int T,
                 hipStream_t s) {

@@ -11,6 +11,7 @@
 #include "stft.hpp"
 #include "tacotron2.hpp"
 #include "wino_consts.hpp"
+#include "xtts_gpt.hpp"
 
 namespace tts {
 
@@ -394,6 +395,13 @@ void pack_skinny_rows(const float* w, int R, int K, bool bf16, float* out) {
   TTS_REQUIRE(R >= 1 && K >= 1 && w, 1, "skinny product: bad weights");
   pack_skinny(ceil_div(R, kSkinnyRows), K, bf16, out,
               [&](int row, int k) { return row < R ? w[(int64_t)row * K + k] : 0.f; });
+}
+
+// HF Conv1D (xtts_gpt.hpp): w [K][R], y = x w + b, so packed row `row` is column `row` of w
+void pack_skinny_cols(const float* w, int K, int R, bool bf16, float* out) {
+  TTS_REQUIRE(R >= 1 && K >= 1 && w, 1, "skinny product: bad weights");
+  pack_skinny(ceil_div(R, kSkinnyRows), K, bf16, out,
+              [&](int row, int k) { return row < R ? w[(int64_t)k * R + row] : 0.f; });
 }
 
 }  // namespace tts

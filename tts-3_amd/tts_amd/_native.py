@@ -288,6 +288,29 @@ class TtsSpeakerEncoderCfg(Structure):
     ]
 
 
+XTTS_GPT_MAX_BATCH = 32
+XTTS_GPT_MAX_AUDIO_TOKENS = 8194
+
+
+class TtsXttsGptCfg(Structure):
+    _fields_ = [
+        ("layers", c_int),
+        ("model_dim", c_int),
+        ("heads", c_int),
+        ("n_text_tokens", c_int),
+        ("n_audio_tokens", c_int),
+        ("start_text_token", c_int),
+        ("stop_text_token", c_int),
+        ("start_audio_token", c_int),
+        ("stop_audio_token", c_int),
+        ("text_positions", c_int),
+        ("mel_positions", c_int),
+        ("prompt_positions", c_int),
+        ("chunk", c_int),
+        ("math_mode", c_int),
+    ]
+
+
 class TtsLaunchRecord(Structure):
     _fields_ = [("name", c_char * 48), ("flops", c_double), ("bytes", c_double), ("ms", c_float)]
 
@@ -573,6 +596,40 @@ SIGNATURES = {
     "tts_speaker_encoder_features": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
     "tts_stft_create_centered": (c_int, [POINTER(TtsStftCfg), c_void_p, c_int, POINTER(c_void_p)]),
     "tts_stft_num_frames_centered": (c_int, [POINTER(TtsStftCfg), c_int64]),
+    "tts_xtts_gpt_num_weights": (c_int, [POINTER(TtsXttsGptCfg)]),
+    "tts_xtts_gpt_weight_numel": (c_int64, [POINTER(TtsXttsGptCfg), c_int]),
+    "tts_xtts_gpt_create": (c_int, [POINTER(TtsXttsGptCfg), POINTER(c_void_p), c_int, POINTER(c_void_p)]),
+    "tts_xtts_gpt_destroy": (c_int, [c_void_p]),
+    "tts_xtts_gpt_prefill": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "tts_xtts_gpt_prefill_profiled": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, POINTER(TtsLaunchRecord), c_int,
+         POINTER(c_int)],
+    ),
+    "tts_xtts_gpt_generate": (
+        c_int,
+        [c_void_p, c_int, c_float, c_float, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+         POINTER(c_int), c_void_p],
+    ),
+    "tts_xtts_gpt_generate_profiled": (
+        c_int,
+        [c_void_p, c_int, c_float, c_float, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+         POINTER(c_int), c_void_p, POINTER(TtsLaunchRecord), c_int, POINTER(c_int)],
+    ),
+    "tts_xtts_gpt_latents": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "tts_xtts_gpt_latents_profiled": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, POINTER(TtsLaunchRecord), c_int,
+         POINTER(c_int)],
+    ),
+    "tts_op_gpt_decode_attn": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
+    ),
+    "tts_op_gpt_decode_attn_waves": (c_int, []),
+    "tts_op_mha_causal": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "tts_op_gpt_sample": (
+        c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_float, c_float, c_int, c_float, c_void_p, c_void_p]
+    ),
 }
 
 _lib = None
