@@ -1125,6 +1125,109 @@ int tts_op_gpt_sample(const float* d_logits, int B, int V, int32_t* d_codes, int
                       float repetition_penalty, float temperature, int top_k, float top_p, const float* d_uniforms,
                       void* hip_stream);
 
+/* ---- XTTS conditioning (TTS/tts/layers/xtts/latent_encoder.py ConditioningEncoder, perceiver_encoder.py
+ * PerceiverResampler, TTS/tts/models/xtts.py wav_to_mel_cloning): reference mel -> the GPT's
+ * conditioning latents, the GPT half of Xtts.get_conditioning_latents ----
+ * style_emb is a chain of launches on the caller's stream:
+ *   init:       the 1x1 conv spec_dim -> model_dim (1 launch);
+ *   per block:  GroupNorm | qkv conv (rows permuted at pack time from the reference's head-major interleaved
+ *               order into q | k | v) | flash attention (tts_op_mha_wide) | proj_out conv + the normalised
+ *               input as residual (4 launches);
+ *   latents:    the learned latents copied to every batch item (1 launch);
+ *   per layer:  to_q | to_kv on the latents | to_kv on the context | cross-attention over the two key buffers |
+ *               to_out + residual | FF product with the GEGLU epilogue | FF product + residual (7 launches);
+ *   RMSNorm (1 launch).
+ * The latents are kept as planes [B][E][num_latents].  The encoder's products and to_kv on the context are
+ * 1x1 convs of the shared conv path; the products over the latent columns are a kernel of their own.
+ * math_mode TTS_MATH_BF16: the convs and the self-attention take bf16 operands, the products over the latent
+ * columns stream bf16-stored matrices against fp32 activations; every other mode runs the convs and the
+ * attention fp32x6 and those products in fp32 FMA.  GroupNorm, the cross-attention, GEGLU, RMSNorm and the
+ * mel front end are fp32-faithful in every mode.  Row b does not depend on B and a repeated call returns the
+ * same bits.
+ * Limits (TTS_ERR_UNSUPPORTED, before any launch): model_dim <= 2048 with a head size model_dim / heads
+ * of 32, 64 or 128; num_latents <= TTS_XTTS_COND_MAX_LATENTS; perceiver_dim_head <= 256 and
+ * perceiver_heads * perceiver_dim_head <= 4096; attn_blocks <= 64; perceiver_depth <= 64; spec_dim <= 1024;
+ * ff_mult <= 16; n_fft, hop_length and win_length inside TtsStftCfg's limits; per call B <=
+ * TTS_XTTS_COND_MAX_BATCH and num_latents + T <= TTS_XTTS_COND_MAX_KEYS (the cross-attention keeps a score
+ * row in LDS); a clip of at least n_fft / 2 + 1 samples (the reflect padding) and below 2 GiB. */
+#define TTS_XTTS_COND_MAX_BATCH 64
+#define TTS_XTTS_COND_MAX_LATENTS 64
+#define TTS_XTTS_COND_MAX_KEYS 8192
+typedef struct TtsXttsCondCfg {
+  int spec_dim;                 /* 80 */
+  int model_dim, heads;         /* 1024, 16 */
+  int attn_blocks;              /* 6 */
+  int perceiver_depth;          /* 2 */
+  int num_latents;              /* 32 */
+  int perceiver_dim_head;       /* 64 */
+  int perceiver_heads;          /* 8 */
+  int ff_mult;                  /* 4: the FF's inner width is int(model_dim * ff_mult * 2 / 3) */
+  int n_fft, hop_length, win_length; /* 2048, 256, 1024 */
+  int math_mode;
+} TtsXttsCondCfg;
+
+/* Host weight order, E = model_dim, inner = perceiver_heads * perceiver_dim_head, I the FF's inner width:
+ *   conditioning_encoder: init.weight [E][spec_dim][1], init.bias; per block attn.{i}: norm.weight,
+ *     norm.bias, qkv.weight [3E][E][1], qkv.bias, proj_out.weight [E][E][1], proj_out.bias (as stored);
+ *   conditioning_perceiver: latents [num_latents][E]; per layer layers.{i}: 0.to_q.weight [inner][E],
+ *     0.to_kv.weight [2 inner][E], 0.to_out.weight [E][inner], 1.0.weight [2I][E], 1.0.bias,
+ *     1.2.weight [E][I], 1.2.bias; norm.gamma [E];
+ *   the front end: the STFT window [win_length], the mel filterbank fb [n_fft/2 + 1][spec_dim]. */
+int tts_xtts_cond_num_weights(const TtsXttsCondCfg* cfg);
+int64_t tts_xtts_cond_weight_numel(const TtsXttsCondCfg* cfg, int index);
+int tts_xtts_cond_create(const TtsXttsCondCfg* cfg, const float* const* host_weights, int device, void** handle);
+int tts_xtts_cond_destroy(void* handle);
+/* Frames T = 1 + N / hop_length of an N-sample clip (centred STFT, reflect padding n_fft / 2: N > n_fft / 2);
+ * -TTS_ERR_* outside the limits. */
+int64_t tts_xtts_cond_num_frames(const void* handle, int64_t N);
+/* wav_to_mel_cloning: d_mel [B][spec_dim][T] = log(max(fb^T |STFT(d_wav)|^2, 1e-5)) / d_mel_norms[:, None];
+ * d_wav [B][N] at the clip's 22 050 Hz, d_mel_norms [spec_dim] (the checkpoint's mel_stats). */
+int tts_xtts_cond_mel(void* handle, const float* d_wav, int B, int64_t N, const float* d_mel_norms, float* d_mel,
+                      void* hip_stream);
+/* get_style_emb: d_mel [B][spec_dim][T] -> d_out [B][E][num_latents].  No host synchronisation. */
+int tts_xtts_cond_style_emb(void* handle, const float* d_mel, int B, int T, float* d_out, void* hip_stream);
+int tts_xtts_cond_style_emb_profiled(void* handle, const float* d_mel, int B, int T, float* d_out, void* hip_stream,
+                                     TtsLaunchRecord* records, int max_records, int* n_records);
+
+/* torchaudio.functional.resample (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99) as a polyphase
+ * product: with o = orig_freq / gcd, n = new_freq / gcd, base = min(o, n) 0.99 and w = ceil(6 o / base),
+ * y[f n + p] = sum_k kern[p][k] xpad[f o + k] over the 2 w + o taps, xpad = x with w zeros in front, cut to
+ * ceil(n N / o) samples (tts_resample_num_samples).  The table is built on the host in fp64 and stored
+ * fp32; a sample's sum runs in fp64 in tap order.  o, n <= TTS_RESAMPLE_MAX_FACTOR, rows below 2^31
+ * samples (TTS_ERR_UNSUPPORTED otherwise).  d_x [B][N] -> d_y [B][ceil(n N / o)]. */
+#define TTS_RESAMPLE_MAX_FACTOR 1024
+int tts_resample_create(int orig_freq, int new_freq, int device, void** handle);
+int tts_resample_destroy(void* handle);
+int64_t tts_resample_num_samples(const void* handle, int64_t N);
+int tts_resample_forward(void* handle, const float* d_x, int B, int64_t N, float* d_y, void* hip_stream);
+
+/* Kernel-test entries of the conditioning path; all device pointers unless named h_.
+ * GroupNorm(groups, C, eps) with the affine over planes d_x [B][C][T]: two-pass statistics per
+ * (b, group), one workgroup each; C % groups == 0, planes below 2 GiB. */
+int tts_op_groupnorm(const float* d_x, int B, int C, int T, int groups, const float* d_gamma, const float* d_beta,
+                     float eps, float* d_y, void* hip_stream);
+/* tts_op_mha past its 512 channels: head sizes 32, 64 or 128 with E <= 2048 (TTS_ERR_UNSUPPORTED
+ * otherwise); arguments, layouts, math modes and tile as tts_op_mha, and the same bits where both accept.
+ * What tts_op_mha and tts_op_mha_causal accept is unchanged. */
+int tts_op_mha_wide(const float* d_qkv, const int64_t* d_key_lengths, int B, int E, int heads, int T, int math_mode,
+                    float* d_out, void* hip_stream);
+/* The perceiver's attention: L latent queries d_q [B][heads dim_head][L] against the L + T keys of
+ * d_kv_lat [B][2 heads dim_head][L] (first) and d_kv_ctx [B][2 heads dim_head][T] (k rows, then v rows),
+ * softmax(q k^T dim_head^-0.5) v -> d_out [B][heads dim_head][L]; fp32.  L <= TTS_XTTS_COND_MAX_LATENTS,
+ * dim_head <= 256, L + T <= TTS_XTTS_COND_MAX_KEYS. */
+int tts_op_cross_attn(const float* d_q, const float* d_kv_lat, const float* d_kv_ctx, int B, int heads, int dim_head,
+                      int L, int T, float* d_out, void* hip_stream);
+/* The perceiver's feed-forward with its residual over planes d_x [B][E][L]: d_out = d_x + W2 (gelu_erf(gate)
+ * a) + b2 with [a | gate] = W0 d_x + b0; h_w0 [2I][E], h_b0 [2I], h_w2 [E][I], h_b2 [E] on the host;
+ * B <= TTS_XTTS_COND_MAX_BATCH, E <= 4096, 1 <= I <= 16384, L <= TTS_XTTS_COND_MAX_LATENTS
+ * (TTS_ERR_UNSUPPORTED otherwise); I need not be a multiple of anything.
+ * Two launches of the perceiver's product kernel: W0 with the GEGLU epilogue, then W2 with the bias and the
+ * residual.  math_mode TTS_MATH_BF16: bf16-stored matrices, fp32 activations and accumulation. */
+int tts_op_cond_ff(const float* d_x, int B, int E, int I, int L, const float* h_w0, const float* h_b0,
+                   const float* h_w2, const float* h_b2, int math_mode, float* d_out, void* hip_stream);
+/* d_y[b][:][l] = d_x[b][:][l] / max(||d_x[b][:][l]||_2, 1e-12) sqrt(E) d_gamma over planes [B][E][L]. */
+int tts_op_rmsnorm(const float* d_x, int B, int E, int L, const float* d_gamma, float* d_y, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,7 @@
 #include "tacotron2.hpp"
 #include "text.hpp"
 #include "vits.hpp"
+#include "xtts_cond.hpp"
 #include "xtts_gpt.hpp"
 #include "tts_mi355x.h"
 
@@ -1214,6 +1215,115 @@ int tts_op_gpt_sample(const float* d_logits, int B, int V, int32_t* d_codes, int
   return guarded([&] {
     tts::op_gpt_sample(d_logits, B, V, d_codes, n_prev, start_audio_token, repetition_penalty, temperature, top_k,
                        top_p, d_uniforms, static_cast<hipStream_t>(hip_stream));
+  });
+}
+
+// ----------------------------------------------------------------------------- XTTS conditioning
+int tts_xtts_cond_num_weights(const TtsXttsCondCfg* cfg) {
+  return num_weights(cfg, tts::xtts_cond_validate, tts::xtts_cond_weight_shapes);
+}
+
+int64_t tts_xtts_cond_weight_numel(const TtsXttsCondCfg* cfg, int idx) {
+  return weight_numel(cfg, idx, tts::xtts_cond_validate, tts::xtts_cond_weight_shapes);
+}
+
+int tts_xtts_cond_create(const TtsXttsCondCfg* cfg, const float* const* host_weights, int device, void** handle) {
+  return create<tts::XttsCond>(cfg, host_weights, device, handle);
+}
+
+int tts_xtts_cond_destroy(void* handle) { return destroy<tts::XttsCond>(handle); }
+
+int64_t tts_xtts_cond_num_frames(const void* handle, int64_t N) {
+  int64_t T = -1;
+  int st = guarded([&] {
+    TTS_REQUIRE(handle, 1, "NULL handle");
+    T = static_cast<const tts::XttsCond*>(handle)->num_frames(N);
+  });
+  return st == TTS_OK ? T : -st;
+}
+
+int tts_xtts_cond_mel(void* handle, const float* d_wav, int B, int64_t N, const float* d_mel_norms, float* d_mel,
+                      void* hip_stream) {
+  return guarded([&] {
+    TTS_REQUIRE(handle, 1, "NULL handle");
+    static_cast<tts::XttsCond*>(handle)->mel(d_wav, B, N, d_mel_norms, d_mel, static_cast<hipStream_t>(hip_stream));
+  });
+}
+
+int tts_xtts_cond_style_emb(void* handle, const float* d_mel, int B, int T, float* d_out, void* hip_stream) {
+  return guarded([&] {
+    TTS_REQUIRE(handle, 1, "NULL handle");
+    static_cast<tts::XttsCond*>(handle)->style_emb(d_mel, B, T, d_out, static_cast<hipStream_t>(hip_stream));
+  });
+}
+
+int tts_xtts_cond_style_emb_profiled(void* handle, const float* d_mel, int B, int T, float* d_out, void* hip_stream,
+                                     TtsLaunchRecord* records, int max_records, int* n_records) {
+  auto body = [&](tts::XttsCond& h, hipStream_t s, tts::Profiler* prof) { h.style_emb(d_mel, B, T, d_out, s, prof); };
+  return profiled<tts::XttsCond>(handle, hip_stream, records, max_records, n_records, body);
+}
+
+int tts_resample_create(int orig_freq, int new_freq, int device, void** handle) {
+  return guarded([&] {
+    TTS_REQUIRE(handle, 1, "NULL argument");
+    *handle = nullptr;
+    *handle = new tts::Resampler(orig_freq, new_freq, device);
+  });
+}
+
+int tts_resample_destroy(void* handle) { return destroy<tts::Resampler>(handle); }
+
+int64_t tts_resample_num_samples(const void* handle, int64_t N) {
+  int64_t n = -1;
+  int st = guarded([&] {
+    TTS_REQUIRE(handle, 1, "NULL handle");
+    n = static_cast<const tts::Resampler*>(handle)->num_samples(N);
+  });
+  return st == TTS_OK ? n : -st;
+}
+
+int tts_resample_forward(void* handle, const float* d_x, int B, int64_t N, float* d_y, void* hip_stream) {
+  return guarded([&] {
+    TTS_REQUIRE(handle, 1, "NULL handle");
+    static_cast<tts::Resampler*>(handle)->forward(d_x, B, N, d_y, static_cast<hipStream_t>(hip_stream));
+  });
+}
+
+int tts_op_groupnorm(const float* d_x, int B, int C, int T, int groups, const float* d_gamma, const float* d_beta,
+                     float eps, float* d_y, void* hip_stream) {
+  return guarded([&] {
+    tts::launch_cond_groupnorm(d_x, d_gamma, d_beta, B, C, T, groups, eps, d_y, static_cast<hipStream_t>(hip_stream));
+  });
+}
+
+int tts_op_mha_wide(const float* d_qkv, const int64_t* d_key_lengths, int B, int E, int heads, int T, int math_mode,
+                    float* d_out, void* hip_stream) {
+  return guarded([&] {
+    TTS_REQUIRE(d_qkv && d_out, 1, "NULL argument");
+    TTS_REQUIRE(math_mode >= tts::MATH_FP32 && math_mode <= tts::MATH_LAST, 1, "unknown math_mode");
+    const int mode = math_mode == tts::MATH_BF16 ? tts::MATH_BF16 : tts::MATH_FP32_X6;
+    tts::launch_mha_wide(mode, d_qkv, d_key_lengths, d_out, B, E, heads, T, static_cast<hipStream_t>(hip_stream));
+  });
+}
+
+int tts_op_cross_attn(const float* d_q, const float* d_kv_lat, const float* d_kv_ctx, int B, int heads, int dim_head,
+                      int L, int T, float* d_out, void* hip_stream) {
+  return guarded([&] {
+    tts::launch_cond_cross_attn(d_q, d_kv_lat, d_kv_ctx, B, heads, dim_head, L, T, d_out,
+                                static_cast<hipStream_t>(hip_stream));
+  });
+}
+
+int tts_op_cond_ff(const float* d_x, int B, int E, int I, int L, const float* h_w0, const float* h_b0,
+                   const float* h_w2, const float* h_b2, int math_mode, float* d_out, void* hip_stream) {
+  return guarded([&] {
+    tts::op_cond_ff(d_x, B, E, I, L, h_w0, h_b0, h_w2, h_b2, math_mode, d_out, static_cast<hipStream_t>(hip_stream));
+  });
+}
+
+int tts_op_rmsnorm(const float* d_x, int B, int E, int L, const float* d_gamma, float* d_y, void* hip_stream) {
+  return guarded([&] {
+    tts::launch_cond_rmsnorm(d_x, d_gamma, B, E, L, d_y, static_cast<hipStream_t>(hip_stream));
   });
 }
 

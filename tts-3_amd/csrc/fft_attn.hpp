@@ -33,4 +33,9 @@ constexpr int kMhaCausalMaxE = 2048;
 void launch_mha_causal(int mode, const float* qkv, const int64_t* key_len, float* out, int B, int E, int heads, int T,
                        hipStream_t s);
 
+// launch_mha's kernel at the causal variant's limits (head sizes 32, 64, 128 with E <= kMhaCausalMaxE), no
+// mask but key_len: the XTTS conditioning encoder's self-attention.  Bitwise launch_mha where both accept.
+void launch_mha_wide(int mode, const float* qkv, const int64_t* key_len, float* out, int B, int E, int heads, int T,
+                     hipStream_t s);
+
 }  // namespace tts

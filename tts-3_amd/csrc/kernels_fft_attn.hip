@@ -335,6 +335,35 @@ void launch_mha_causal(int mode, const float* qkv, const int64_t* key_len, float
   TTS_HIP_CHECK(hipGetLastError());
 }
 
+template <class S>
+void launch_mha_wide_s(int dk, const MhaArgs& a, const dim3& grid, hipStream_t s) {
+  switch (dk) {
+    case 32: launch_mha_k<S, 32>(a, grid, s); break;
+    case 64: launch_mha_k<S, 64>(a, grid, s); break;
+    default: launch_mha_k<S, 128>(a, grid, s); break;
+  }
+}
+
+// The non-causal kernel past launch_mha's 512 channels (the XTTS conditioning encoder: 1024 channels in
+// 16 heads): the same instantiations, so a shape both accept gives the same bits.
+void launch_mha_wide(int mode, const float* qkv, const int64_t* key_len, float* out, int B, int E, int heads, int T,
+                     hipStream_t s) {
+  TTS_REQUIRE(mode == MATH_FP32_X6 || mode == MATH_BF16, 3, "mha: math mode must be fp32x6 or bf16");
+  TTS_REQUIRE(B >= 1 && E >= 1 && heads >= 1 && T >= 1, 1, "mha: bad shape");
+  TTS_REQUIRE(E % heads == 0, 1, "mha: the channels must divide into the heads");
+  const int dk = E / heads;
+  TTS_REQUIRE(E <= kMhaCausalMaxE && (dk == 32 || dk == 64 || dk == 128), 3,
+              "wide mha: head size must be one of 32, 64, 128 with at most 2048 channels");
+  TTS_REQUIRE(B <= 65535 && heads <= 65535, 3, "mha: batch size and heads must lie in [1, 65535]");
+  TTS_REQUIRE((int64_t)3 * E * T * 4 < (int64_t)1 << 31, 3, "mha: a batch item's qkv plane exceeds 2 GiB");
+  TTS_REQUIRE(qkv != out, 1, "mha: the output must not alias the input");
+  MhaArgs a{qkv, key_len, out, E, T, kLog2e / sqrtf((float)dk)};
+  const dim3 grid((T + kMhaTile - 1) / kMhaTile, heads, B);
+  if (mode == MATH_BF16) launch_mha_wide_s<SchemeB1>(dk, a, grid, s);
+  else launch_mha_wide_s<SchemeX6>(dk, a, grid, s);
+  TTS_HIP_CHECK(hipGetLastError());
+}
+
 void launch_mha(int mode, const float* qkv, const int64_t* key_len, float* out, int B, int E, int heads, int T,
                 hipStream_t s) {
   TTS_REQUIRE(mode == MATH_FP32_X6 || mode == MATH_BF16, 3, "mha: math mode must be fp32x6 or bf16");

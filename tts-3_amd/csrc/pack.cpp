@@ -11,6 +11,7 @@
 #include "stft.hpp"
 #include "tacotron2.hpp"
 #include "wino_consts.hpp"
+#include "xtts_cond.hpp"
 #include "xtts_gpt.hpp"
 
 namespace tts {
@@ -402,6 +403,71 @@ void pack_skinny_cols(const float* w, int K, int R, bool bf16, float* out) {
   TTS_REQUIRE(R >= 1 && K >= 1 && w, 1, "skinny product: bad weights");
   pack_skinny(ceil_div(R, kSkinnyRows), K, bf16, out,
               [&](int row, int k) { return row < R ? w[(int64_t)k * R + row] : 0.f; });
+}
+
+// ---- XTTS conditioning (xtts_cond.hpp) ----
+int cond_groupnorm_groups(int channels) {
+  int g = 32;
+  if (channels <= 16) g = 8;
+  else if (channels <= 64) g = 16;
+  while (g > 1 && channels % g != 0) g /= 2;
+  return g;
+}
+
+int cond_qkv_source_row(int r, int E, int heads) {
+  const int dk = E / heads;
+  const int part = r / E, c = r % E;  // part: 0 q, 1 k, 2 v
+  const int h = c / dk, d = c % dk;
+  return h * 3 * dk + part * dk + d;
+}
+
+void pack_cond_qkv(const float* w, const float* b, int E, int heads, float* w_out, float* b_out) {
+  TTS_REQUIRE(w && b && w_out && b_out, 1, "qkv permutation: NULL argument");
+  TTS_REQUIRE(E >= 1 && heads >= 1 && E % heads == 0, 1, "qkv permutation: the channels must divide into the heads");
+  for (int r = 0; r < 3 * E; ++r) {
+    const int src = cond_qkv_source_row(r, E, heads);
+    std::memcpy(w_out + (size_t)r * E, w + (size_t)src * E, (size_t)E * sizeof(float));
+    b_out[r] = b[src];
+  }
+}
+
+int64_t cond_rows_numel(int64_t n, bool bf16) { return bf16 ? (n + 1) / 2 : n; }
+
+void pack_cond_rows(const float* w, int64_t n, bool bf16, float* out) {
+  TTS_REQUIRE(w && out && n >= 1, 1, "perceiver matrix: bad weights");
+  if (!bf16) {
+    std::memcpy(out, w, (size_t)n * sizeof(float));
+    return;
+  }
+  uint16_t* o = reinterpret_cast<uint16_t*>(out);
+  for (int64_t i = 0; i < n; ++i) {
+    uint32_t u;
+    std::memcpy(&u, &w[i], 4);
+    u += 0x7fffu + ((u >> 16) & 1u);  // round to nearest even
+    o[i] = (uint16_t)(u >> 16);
+  }
+  if (n & 1) o[n] = 0;
+}
+
+int resample_width(int o, int n) {
+  const double base = std::min(o, n) * 0.99;
+  return (int)std::ceil(6.0 * o / base);
+}
+
+void build_resample_table(int o, int n, float* out) {
+  TTS_REQUIRE(o >= 1 && n >= 1 && out, 1, "resample: bad ratio");
+  const double kPi = 3.14159265358979323846;
+  const double base = std::min(o, n) * 0.99;
+  const int w = resample_width(o, n), taps = 2 * w + o;
+  for (int p = 0; p < n; ++p)
+    for (int k = 0; k < taps; ++k) {
+      double t = (-(double)p / n + (double)(k - w) / o) * base;
+      t = std::max(-6.0, std::min(6.0, t));
+      const double c = std::cos(t * kPi / 12.0);
+      const double a = t * kPi;
+      const double sinc = a == 0.0 ? 1.0 : std::sin(a) / a;
+      out[(size_t)k * n + p] = (float)(sinc * c * c * base / o);
+    }
 }
 
 }  // namespace tts

@@ -311,6 +311,30 @@ class TtsXttsGptCfg(Structure):
     ]
 
 
+XTTS_COND_MAX_BATCH = 64
+XTTS_COND_MAX_LATENTS = 64
+XTTS_COND_MAX_KEYS = 8192
+RESAMPLE_MAX_FACTOR = 1024
+
+
+class TtsXttsCondCfg(Structure):
+    _fields_ = [
+        ("spec_dim", c_int),
+        ("model_dim", c_int),
+        ("heads", c_int),
+        ("attn_blocks", c_int),
+        ("perceiver_depth", c_int),
+        ("num_latents", c_int),
+        ("perceiver_dim_head", c_int),
+        ("perceiver_heads", c_int),
+        ("ff_mult", c_int),
+        ("n_fft", c_int),
+        ("hop_length", c_int),
+        ("win_length", c_int),
+        ("math_mode", c_int),
+    ]
+
+
 class TtsLaunchRecord(Structure):
     _fields_ = [("name", c_char * 48), ("flops", c_double), ("bytes", c_double), ("ms", c_float)]
 
@@ -630,6 +654,32 @@ SIGNATURES = {
     "tts_op_gpt_sample": (
         c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_float, c_float, c_int, c_float, c_void_p, c_void_p]
     ),
+    "tts_xtts_cond_num_weights": (c_int, [POINTER(TtsXttsCondCfg)]),
+    "tts_xtts_cond_weight_numel": (c_int64, [POINTER(TtsXttsCondCfg), c_int]),
+    "tts_xtts_cond_create": (c_int, [POINTER(TtsXttsCondCfg), POINTER(c_void_p), c_int, POINTER(c_void_p)]),
+    "tts_xtts_cond_destroy": (c_int, [c_void_p]),
+    "tts_xtts_cond_num_frames": (c_int64, [c_void_p, c_int64]),
+    "tts_xtts_cond_mel": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
+    "tts_xtts_cond_style_emb": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "tts_xtts_cond_style_emb_profiled": (
+        c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, POINTER(TtsLaunchRecord), c_int, POINTER(c_int)]
+    ),
+    "tts_resample_create": (c_int, [c_int, c_int, c_int, POINTER(c_void_p)]),
+    "tts_resample_destroy": (c_int, [c_void_p]),
+    "tts_resample_num_samples": (c_int64, [c_void_p, c_int64]),
+    "tts_resample_forward": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
+    "tts_op_groupnorm": (
+        c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p]
+    ),
+    "tts_op_mha_wide": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "tts_op_cross_attn": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
+    ),
+    "tts_op_cond_ff": (
+        c_int,
+        [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
+    ),
+    "tts_op_rmsnorm": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -7,9 +7,9 @@
 names and ``Conv1D`` weights stored ``[in][out]``, ``gpt.ln_f``, ``final_norm``, ``text_head``, ``mel_head``)
 and runs ``generate`` (text tokens + conditioning latents -> audio codes) and ``forward(...,
 return_latent=True)`` (codes -> the decoder's latents) through ``tts_xtts_gpt_*``.  The conditioning
-latents are an input, as they are for the reference's ``Xtts.inference``; the conditioning encoder, the
-perceiver resampler, the tokenizer, beam search, ``inference_stream`` and training stay out (DESIGN.md
-section 8).
+latents are an input, as they are for the reference's ``Xtts.inference``; ``Xtts.get_conditioning_latents``
+computes them from reference clips with an ``XttsConditioning`` (``xtts_cond.py``).  The tokenizer, beam
+search, ``inference_stream``, audio file loading and training stay out.
 
 Sampling draws by inverse CDF from uniforms ``torch.rand(B, max_new_tokens, generator=generator)``: the
 reference's distribution, not ``torch.multinomial``'s stream of draws.  Extensions to the reference's
@@ -413,13 +413,105 @@ def _profiled(fn: str, args) -> List[Dict]:
 
 
 class Xtts(nn.Module):
-    """``TTS/tts/models/xtts.py`` ``Xtts.inference`` on token ids: ``XttsGPT`` -> latents -> ``HifiDecoder``."""
+    """``TTS/tts/models/xtts.py`` ``Xtts.inference`` on token ids: ``XttsGPT`` -> latents -> ``HifiDecoder``,
+    and, with ``conditioning`` (an ``XttsConditioning``) and ``mel_stats`` (the checkpoint's buffer),
+    ``get_conditioning_latents`` on reference clips that are already device tensors."""
 
-    def __init__(self, gpt: XttsGPT, hifigan_decoder: HifiDecoder, gpt_max_new_tokens: Optional[int] = None):
+    def __init__(self, gpt: XttsGPT, hifigan_decoder: HifiDecoder, gpt_max_new_tokens: Optional[int] = None,
+                 conditioning=None, mel_stats: Optional[torch.Tensor] = None):
         super().__init__()
         self.gpt = gpt
         self.hifigan_decoder = hifigan_decoder
         self.gpt_max_new_tokens = gpt_max_new_tokens
+        if conditioning is not None:  # opt-in: the default module tree is unchanged
+            self.conditioning = conditioning
+            stats = torch.ones(conditioning.spec_dim) if mel_stats is None else torch.as_tensor(mel_stats)
+            self.register_buffer("mel_stats", stats.detach().to(torch.float32).reshape(-1).clone())
+
+    # ------------------------------------------------------------------ voice cloning
+    def _conditioning(self):
+        cond = getattr(self, "conditioning", None)
+        if cond is None:
+            raise RuntimeError("this Xtts was built without its conditioning encoder / perceiver: pass "
+                               "conditioning=XttsConditioning(...)")
+        return cond
+
+    @staticmethod
+    def _clip(audio, what="audio") -> torch.Tensor:
+        if isinstance(audio, (str, bytes)) or hasattr(audio, "__fspath__"):
+            raise NotImplementedError(f"loading {what} from a file path is {_EXCLUDED}: pass the clip as a [1, N] tensor")
+        _nat.require_device_tensor(audio, what)
+        if audio.dim() == 1:
+            audio = audio.unsqueeze(0)
+        if audio.dim() != 2 or audio.shape[0] != 1 or audio.shape[1] < 1:
+            raise ValueError(f"{what} must be a [1, N] tensor, got shape {tuple(audio.shape)}")
+        return audio.to(torch.float32)
+
+    @torch.no_grad()
+    def get_gpt_cond_latents(self, audio, sr, length: int = 30, chunk_length: int = 6):
+        """xtts.py ``get_gpt_cond_latents`` (the perceiver path): audio [1, N] at ``sr`` -> [1, num_latents, E],
+        the mean over the clip's ``chunk_length``-second chunks of ``get_style_emb`` of their mels."""
+        from ..audio import resample
+
+        cond = self._conditioning()
+        audio = self._clip(audio)
+        if int(sr) != 22050:
+            audio = resample(audio, int(sr), 22050)
+        if length > 0:
+            audio = audio[:, : 22050 * int(length)]
+        step = 22050 * int(chunk_length)
+        if step < 1:
+            raise ValueError("chunk_length must be positive")
+        total, n = None, 0
+        for i in range(0, audio.shape[1], step):
+            chunk = audio[:, i : i + step]
+            if chunk.shape[-1] < 22050 * 0.33:  # the reference skips a too short last chunk
+                continue
+            mel = cond.wav_to_mel_cloning(chunk, self.mel_stats)
+            emb = cond.get_style_emb(mel)
+            total = emb if total is None else total + emb  # chunk order: one fixed order of the sum
+            n += 1
+        if n == 0:
+            raise ValueError("the reference clip is shorter than 0.33 s: no chunk is left")
+        return (total / n).transpose(1, 2)
+
+    @torch.no_grad()
+    def get_speaker_embedding(self, audio, sr):
+        """xtts.py ``get_speaker_embedding``: audio [1, N] at ``sr`` -> [1, d_vector_dim, 1] (resampled to 16 kHz)."""
+        from ..audio import resample
+
+        if getattr(self.hifigan_decoder, "speaker_encoder", None) is None:
+            raise RuntimeError("the HifiDecoder was built without its speaker encoder: pass with_speaker_encoder=True")
+        audio_16k = resample(self._clip(audio), int(sr), 16000)
+        return self.hifigan_decoder.speaker_embedding(audio_16k)
+
+    @torch.no_grad()
+    def get_conditioning_latents(self, audio_path, max_ref_length=30, gpt_cond_len=6, gpt_cond_chunk_len=6,
+                                 librosa_trim_db=None, sound_norm_refs=False, load_sr=22050):
+        """xtts.py ``get_conditioning_latents`` on clips that are already loaded: ``audio_path`` is a [1, N]
+        device tensor at ``load_sr`` or a list of them (file loading and ``librosa_trim_db`` stay on the host).
+        Returns ``(gpt_cond_latent [1, num_latents, E], speaker_embedding [1, d_vector_dim, 1])``."""
+        if librosa_trim_db is not None:
+            raise NotImplementedError(f"librosa_trim_db (trimming the reference clip) is {_EXCLUDED}")
+        clips = audio_path if isinstance(audio_path, (list, tuple)) else [audio_path]
+        if len(clips) == 0:
+            raise ValueError("no reference clip")
+        self._conditioning()
+        audios, embs = [], []
+        for clip in clips:
+            audio = self._clip(clip, "audio_path")[:, : int(load_sr) * int(max_ref_length)]
+            if sound_norm_refs:
+                audio = (audio / torch.abs(audio).max()) * 0.75
+            embs.append(self.get_speaker_embedding(audio, load_sr))
+            audios.append(audio)
+        full_audio = torch.cat(audios, dim=-1)
+        gpt_cond_latents = self.get_gpt_cond_latents(full_audio, load_sr, length=gpt_cond_len,
+                                                     chunk_length=gpt_cond_chunk_len)
+        speaker_embedding = embs[0]
+        for e in embs[1:]:
+            speaker_embedding = speaker_embedding + e
+        speaker_embedding = speaker_embedding / len(embs)
+        return gpt_cond_latents, speaker_embedding
 
     @torch.no_grad()
     def inference(self, text_tokens, gpt_cond_latent, speaker_embedding, temperature=0.75, length_penalty=1.0,
