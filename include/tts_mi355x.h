@@ -669,6 +669,12 @@ int tts_op_conv1d(const TtsConv1dDesc* d, const float* d_x, const float* h_w, co
 int tts_op_conv1d_bench(const TtsConv1dDesc* d, const float* d_x, const float* h_w, const float* h_b,
                         const float* d_res, float* d_y, float* d_z, int tile, int reps, float* ms,
                         void* hip_stream);
+/* The same with a per-item channel vector d_cvec [B][Cout] added to the bias before act_out (the
+ * conditioning term the executors fold into a conv's epilogue), one launch of tile configuration
+ * `tile` (tile < 0: automatic). */
+int tts_op_conv1d_cvec(const TtsConv1dDesc* d, const float* d_x, const float* h_w, const float* h_b,
+                       const float* d_cvec, const float* d_res, float* d_y, float* d_z, int tile,
+                       void* hip_stream);
 /* Number of conv1d tile configurations compiled into the library for a math mode. */
 int tts_op_conv1d_num_tiles(int math_mode);
 

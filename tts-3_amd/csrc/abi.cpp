@@ -653,7 +653,7 @@ int tts_stft_forward_profiled(void* handle, const float* d_wav, int B, int64_t N
 // ----------------------------------------------------------------------------- single ops
 static void op_conv1d_impl(const TtsConv1dDesc* d, const float* d_x, const float* h_w, const float* h_b,
                            const float* d_res, float* d_y, float* d_z, int tile, int reps, float* ms,
-                           void* hip_stream) {
+                           void* hip_stream, const float* d_cvec = nullptr) {
   TTS_REQUIRE(d && d_x && h_w && h_b, 1, "NULL argument");
   TTS_REQUIRE(d->B >= 1 && d->Cin >= 1 && d->Cout >= 1 && d->Tin >= 1 && d->K >= 1 && d->dil >= 1, 1,
               "bad conv1d shape");
@@ -670,7 +670,7 @@ static void op_conv1d_impl(const TtsConv1dDesc* d, const float* d_x, const float
   std::memcpy(bias.data(), h_b, sizeof(float) * d->Cout);
   const tts::DeviceBuffer w = to_device(packed.data(), packed.size()), b = to_device(bias.data(), bias.size());
   tts::Conv1dArgs a{};
-  a.x = d_x; a.w = w.as<>(); a.bias = b.as<>(); a.res = d_res; a.y = d_y; a.z = d_z; a.cvec = nullptr;
+  a.x = d_x; a.w = w.as<>(); a.bias = b.as<>(); a.res = d_res; a.y = d_y; a.z = d_z; a.cvec = d_cvec;
   a.Cin = d->Cin; a.Cout = d->Cout; a.Tin = d->Tin; a.Tout = d->Tin + 2 * d->rep_pad;
   a.dil = d->dil; a.pad = d->dil * (d->K - 1) / 2; a.rep_pad = d->rep_pad;
   a.n_chunks = tts::ceil_div(d->Cin, t.CK);
@@ -714,6 +714,15 @@ int tts_op_conv1d_bench(const TtsConv1dDesc* d, const float* d_x, const float* h
                         const float* d_res, float* d_y, float* d_z, int tile, int reps, float* ms,
                         void* hip_stream) {
   return guarded([&] { op_conv1d_impl(d, d_x, h_w, h_b, d_res, d_y, d_z, tile, reps, ms, hip_stream); });
+}
+
+int tts_op_conv1d_cvec(const TtsConv1dDesc* d, const float* d_x, const float* h_w, const float* h_b,
+                       const float* d_cvec, const float* d_res, float* d_y, float* d_z, int tile,
+                       void* hip_stream) {
+  return guarded([&] {
+    TTS_REQUIRE(d_cvec, 1, "NULL cvec");
+    op_conv1d_impl(d, d_x, h_w, h_b, d_res, d_y, d_z, tile, 0, nullptr, hip_stream, d_cvec);
+  });
 }
 
 int tts_op_conv1d_num_tiles(int math_mode) {

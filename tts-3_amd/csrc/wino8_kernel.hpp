@@ -14,8 +14,8 @@
 //   placed between the MFMA steps of chunk c).
 // * Barriers are bare s_barrier with an explicit lgkmcnt wait: __syncthreads' fence would also
 //   drain the DMA and weight loads in flight.
-// * Epilogue: the two waves of a pair swap their partial point sums through LDS (each finishes
-//   one 32-column block), then store 16-byte vectors of 4 consecutive samples (dilation 1) or
+// * Epilogue: the two waves of a pair swap their partial point sums through LDS in one round (each
+//   finishes one 32-column block), then store 16-byte vectors of 4 consecutive samples (dilation 1) or
 //   transpose their rows through LDS first (dilation 3, 5), as wino_kernel.hpp.
 #pragma once
 
@@ -72,10 +72,20 @@ struct Wino8Cfg {
   static_assert(UPW <= 64 && UNITS <= 256 + 64 && 3 * NCH >= 3, "one transform round per wave; the DMA spreads over 3 steps");
   static_assert(2 * (UNITS - 256) <= 4 * 64, "spread leftover jobs: one per lane of waves 4-7");
   static_assert(TW <= PITCH, "");
-  // the transformed buffers double as the epilogue's exchange (8 waves x 8 rows x 64 lanes x 16 B) and
-  // transpose regions; the bf16 scheme's 48-byte rows need the floor
-  static constexpr int EPI = 4 * 16 * PITCH * 4 > 8 * 8 * 4 * 64 * 4 ? 4 * 16 * PITCH * 4 : 8 * 8 * 4 * 64 * 4;
+  // the transformed buffers double as the epilogue's transpose region (4 pairs x 16 rows x PITCH
+  // samples); the bf16 scheme's 48-byte rows need the floor
+  static constexpr int EPI = 4 * 16 * PITCH * 4;
   static constexpr int TSM = 2 * TSZ > EPI ? 2 * TSZ : EPI;
+  // the epilogue's exchange: every wave hands its partner all 16 registers of one column block at
+  // once (8 waves x 16 rows x 64 lanes x 16 B = 128 KiB), over the transformed buffers, both raw
+  // windows (dead after the last chunk's transform) and, where those are smaller, LDS the main loop
+  // never touches.  The kernel holds its CU alone either way (one workgroup of 512 threads at
+  // 241+ VGPRs), so the larger allocation costs no occupancy
+  static constexpr int XCH = 8 * 16 * 64 * 16;
+  static constexpr int SMEM = TSM + 2 * RSZ > XCH ? TSM + 2 * RSZ : XCH;
+  static constexpr int WBIAS = 128 * 4;  // the staged bias + cvec rows
+  static_assert(TSM % 16 == 0 && RSZ % 16 == 0, "the raw windows start 16-byte aligned behind the transformed buffers");
+  static_assert(SMEM + WBIAS <= 160 * 1024, "one-round exchange: the workgroup's LDS budget (160 KiB per CU)");
 };
 
 // PL: Conv1dArgs::planes (MATH_BF16 only: 0, or bf16 input and bf16 res / z / y)
@@ -115,9 +125,11 @@ __global__ __launch_bounds__(512) void conv1d_wino8_kernel(Conv1dArgs a) {
 #ifndef WINO8_GAP11
 #define WINO8_GAP11 1
 #endif
-  __shared__ __attribute__((aligned(16))) unsigned char tsm[C::TSM];  // transformed planes
-  __shared__ __attribute__((aligned(16))) unsigned char rsm[2 * C::RSZ];  // raw input windows
-  __shared__ float wbias[128];  // bias + cvec of the 128 rows, staged in the prologue (the epilogue
+  // one block, so that the epilogue's exchange may span both parts (Wino8Cfg::XCH)
+  __shared__ __attribute__((aligned(16))) unsigned char smem[C::SMEM];
+  unsigned char* const tsm = smem;            // transformed planes
+  unsigned char* const rsm = smem + C::TSM;   // raw input windows
+  __shared__ float wbias[C::WBIAS / 4];  // bias + cvec of the 128 rows, staged in the prologue (the epilogue
                                 // reads LDS instead of paying an L2 latency per pass)
 
   const int tid = threadIdx.x;
@@ -308,11 +320,7 @@ __global__ __launch_bounds__(512) void conv1d_wino8_kernel(Conv1dArgs a) {
   // transform's sums are those of the point split, so the results are bitwise the same.
   constexpr bool NX = WINO8_NOXCH != 0;
   constexpr int NA = NX ? 7 : 4, NB = NX ? 1 : 2;  // accumulators: points x column blocks
-  f32x16 acc[NA][NB];
-#pragma unroll
-  for (int p = 0; p < NA; ++p)
-#pragma unroll
-    for (int n = 0; n < NB; ++n) acc[p][n] = f32x16{};
+  f32x16 acc[NA][NB];  // zeroed by run(): the group of points 4-6 neither clears nor carries a fourth set
   WSTAMP(0);
 
   float bpre = 0.f;
@@ -361,6 +369,10 @@ __global__ __launch_bounds__(512) void conv1d_wino8_kernel(Conv1dArgs a) {
     constexpr int P0 = decltype(p0_tag)::value;
     constexpr bool G1 = decltype(g1_tag)::value;  // the DMA-issuing group (waves 4-7)
     constexpr int NV = NPG * NCH;  // MFMA steps per chunk for this wave
+#pragma unroll
+    for (int p = 0; p < NPG; ++p)
+#pragma unroll
+      for (int n = 0; n < NB; ++n) acc[p][n] = f32x16{};
     // weight prefetch depth: the DMA-issuing waves (P0 > 0, 96 accumulator registers) prefetch
     // further ahead, so the in-order wait for their input DMA falls PDG steps after its issue
     // the bf16 scheme's steps are a third as long (one product per MAC): its own depths (A/B)
@@ -451,62 +463,93 @@ __global__ __launch_bounds__(512) void conv1d_wino8_kernel(Conv1dArgs a) {
 #endif
   if (WINO8_PRIO == 1 && grp == 1) __builtin_amdgcn_s_setprio(1);
   if (WINO8_PRIO == 2 && grp == 0) __builtin_amdgcn_s_setprio(1);
+  // ---- epilogue, first part: output transform and the pair's exchange ----
+  // Waves w (points 0-3) and w + 4 (points 4-6) hold partial sums of both 32-column blocks; wave w
+  // finishes block 0, wave w + 4 block 1.  Each applies A^T to its own points (the partial outputs
+  // of one accumulator register r are 4 floats), writes the 16 vectors of the block its partner
+  // finishes to its slot [wave][16 r][64 lanes] of 16 B (ds_write_b128 / ds_read_b128, lanes
+  // contiguous: conflict-free), keeps the other block's in y, and after one barrier adds the
+  // partner's 16 vectors.  One straight-line path per point group, taken on the wave-uniform grp
+  // together with the group's main loop: no per-register branch or select, and the accumulators of
+  // a block are dead once its partials are formed.  The sums are those of the NX block below.
+  float y[4][16];
+  auto at_xch = [&](auto g_tag) {
+    constexpr int G = decltype(g_tag)::value;
+    auto part = [&](int n, int r, float(&o)[4]) {
+      if constexpr (G == 0) {
+        const float m0 = acc[0][n][r], m1 = acc[1][n][r], m2 = acc[2][n][r], m3 = acc[3][n][r];
+        const float s12 = m1 + m2, d12 = m1 - m2;
+        o[0] = (m0 + s12) + m3;
+        o[1] = fmaf(2.f, m3, d12);
+        o[2] = fmaf(4.f, m3, s12);
+        o[3] = fmaf(8.f, m3, d12);
+      } else {
+        const float m4 = acc[0][n][r], m5 = acc[1][n][r], m6 = acc[2][n][r];
+        o[0] = m4 + m5;
+        o[1] = fmaf(-2.f, m4, 0.5f * m5);
+        o[2] = fmaf(4.f, m4, 0.25f * m5);
+        o[3] = fmaf(-8.f, m4, 0.125f * m5) + m6;
+      }
+    };
+    // every wave is past its last LDS access of the main loop (the barrier that ends the last
+    // chunk) and every input DMA has landed: the whole block is free, no barrier before the writes
+    f32x4* xch = reinterpret_cast<f32x4*>(smem);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      float o[4];
+      part(1 - G, r, o);
+      xch[((wm * 2 + G) * 16 + r) * 64 + lane] = f32x4{o[0], o[1], o[2], o[3]};
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      float o[4];
+      part(G, r, o);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) y[i][r] = o[i];
+    }
+    WSTAMP(20);
+    lds_sync();
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const f32x4 other = xch[((wm * 2 + (1 - G)) * 16 + r) * 64 + lane];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) y[i][r] = y[i][r] + other[i];
+    }
+    // dilation 3, 5: finish() transposes through the same memory
+    if (D != 1) lds_sync();
+  };
+  constexpr bool EPI_OFF = (WINO_ABLATE & 16) != 0;
   if constexpr (NX) {
     if (grp == 0) run(std::integral_constant<int, 7>{}, std::integral_constant<int, 0>{}, std::false_type{});
     else run(std::integral_constant<int, 7>{}, std::integral_constant<int, 0>{}, std::true_type{});
+  } else if (grp == 0) {
+    run(std::integral_constant<int, 4>{}, std::integral_constant<int, 0>{}, std::false_type{});
+    if (!EPI_OFF) at_xch(std::integral_constant<int, 0>{});
   } else {
-    if (grp == 0) run(std::integral_constant<int, 4>{}, std::integral_constant<int, 0>{}, std::false_type{});
-    else run(std::integral_constant<int, 3>{}, std::integral_constant<int, 4>{}, std::true_type{});
+    run(std::integral_constant<int, 3>{}, std::integral_constant<int, 4>{}, std::true_type{});
+    if (!EPI_OFF) at_xch(std::integral_constant<int, 1>{});
   }
 
-#ifndef WINO8_EPI_PF
-#define WINO8_EPI_PF 0
-#endif
-  // L2 prefetch of the epilogue's gathers (dilation 1: the residual and the MRF sum): every
-  // 128-byte line of this workgroup's 128-row x TW-sample output tile is touched once, right after
-  // the wave's last weight load, so the gathers after the output transform and the partial-sum
-  // exchange hit L2 instead of HBM.  The LDS-DMA writes land in the raw windows, which nothing
-  // reads after the last chunk's transform (the chunk before it)
-  if constexpr (WINO8_EPI_PF && D == 1) {
-    if (a.res || a.zmode >= 2) {
-      constexpr unsigned YES = PlaneT<YB>::ES;
-      constexpr int LPR = C::TW * (int)YES / 128;  // lines per row
-      const unsigned plane = (unsigned)a.Cout * (unsigned)a.Tout * YES;
-      const size_t item = (size_t)b * (a.o_bstride ? a.o_bstride : (int64_t)a.Cout * a.Tout);
-      const void* pres = a.res ? plane_at<YB>(a.res, item) : nullptr;
-      const void* pz = a.zmode >= 2 ? plane_at<YB>(a.z, item) : nullptr;
-#pragma unroll
-      for (int i = 0; i < (128 * LPR + 511) / 512; ++i) {
-        const int l = tid + 512 * i;
-        const int co = mt * 128 + l / LPR, ln = l % LPR;
-        const int t = t0 + ln * (128 / (int)YES);
-        const unsigned vo = (l < 128 * LPR && co < a.Cout && t < a.Tout) ? ((unsigned)co * (unsigned)a.Tout + (unsigned)t) * YES : OOB_OFF;
-        if (pres) l2_touch_dma(pres, plane, vo, rsm);
-        if (pz) l2_touch_dma(pz, plane, vo, rsm + 256);
-      }
-    }
-  }
-
-  // ---- epilogue ----
-  if (WINO_ABLATE & 16) {
+  if (EPI_OFF) {
     float sum = 0.f;
 #pragma unroll
     for (int p = 0; p < NA; ++p)
 #pragma unroll
       for (int n = 0; n < NB; ++n)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) sum += acc[p][n][r];
+        for (int r = 0; r < 16; ++r)
+          if (NX || p < 3 || grp == 0) sum += acc[p][n][r];
     if (sum == 1234.5f) a.y[threadIdx.x] = sum;
     return;
   }
+  // ---- epilogue, second part: bias, activation, residual, MRF sum, stores ----
   // the f16x3 rescale sc (an exact power of two) commutes with the output transform: applied once
   // per output in wino_apply instead of once per point here
   const float sc = H3 ? ldexpf(1.f, ex + a.w_exp) : 1.f;
   const int nk = grp;  // the column block this wave finishes
-  float y[4][16];
   if constexpr (NX) {
     // all 7 points of column block nk in this wave: the point-split sums (points 0-3) + (4-6),
-    // formed exactly as the exchange below forms them
+    // formed exactly as the exchange forms them
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const float m0 = acc[0][0][r], m1 = acc[1][0][r], m2 = acc[2][0][r], m3 = acc[3][0][r];
@@ -518,60 +561,21 @@ __global__ __launch_bounds__(512) void conv1d_wino8_kernel(Conv1dArgs a) {
       y[3][r] = fmaf(8.f, m3, d12) + (fmaf(-8.f, m4, 0.125f * m5) + m6);
     }
     WSTAMP(20);
-  } else {
-  // partial outputs of this wave's points: yp[n][i][r]
-  float yp[2][4][16];
-#pragma unroll
-  for (int n = 0; n < 2; ++n)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      if (grp == 0) {
-        const float m0 = acc[0][n][r], m1 = acc[1][n][r], m2 = acc[2][n][r], m3 = acc[3][n][r];
-        const float s12 = m1 + m2, d12 = m1 - m2;
-        yp[n][0][r] = (m0 + s12) + m3;
-        yp[n][1][r] = fmaf(2.f, m3, d12);
-        yp[n][2][r] = fmaf(4.f, m3, s12);
-        yp[n][3][r] = fmaf(8.f, m3, d12);
-      } else {
-        const float m4 = acc[0][n][r], m5 = acc[1][n][r], m6 = acc[2][n][r];
-        yp[n][0][r] = m4 + m5;
-        yp[n][1][r] = fmaf(-2.f, m4, 0.5f * m5);
-        yp[n][2][r] = fmaf(4.f, m4, 0.25f * m5);
-        yp[n][3][r] = fmaf(-8.f, m4, 0.125f * m5) + m6;
-      }
-    }
-  WSTAMP(20);
-  // swap halves: group 0 finishes column block 0, group 1 block 1 (two passes of 8 rows per lane)
-  // [wm][grp][8 r][64 lanes] float4 (the 4 outputs i of one register r): one ds_write_b128 /
-  // ds_read_b128 per r, lanes contiguous (conflict-free), 64 KiB
-  f32x4* xch = reinterpret_cast<f32x4*>(tsm);
-  lds_sync();  // every wave is past its last LDS read of the main loop
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      f32x4 v;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] = grp == 0 ? yp[1][i][8 * h + r] : yp[0][i][8 * h + r];
-      xch[((wm * 2 + grp) * 8 + r) * 64 + lane] = v;
-    }
-    lds_sync();
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      const f32x4 other = xch[((wm * 2 + (1 - grp)) * 8 + r) * 64 + lane];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) y[i][8 * h + r] = (grp == 0 ? yp[0][i][8 * h + r] : yp[1][i][8 * h + r]) + other[i];
-    }
-    lds_sync();
-  }
   }
 
   WSTAMP(21);
   const int zm = a.zmode <= 1 ? 0 : a.zmode;
   const int cobase = mt * 128 + wm * 32;
-  auto finish = [&](auto res_tag, auto zm_tag) {
+  // FULL: the workgroup's whole tile lies inside Tout and the rows are 16-byte aligned (decided once
+  // per workgroup, below): 16-byte gathers and stores only.  Otherwise (the last column tile, or
+  // Tout % 4 != 0) each lane decides per vector, as wino_kernel.hpp.  OS1: out_slope == 1, no output
+  // activation (max(x, 1 * x) = x bit for bit), FULL tiles only
+  auto finish = [&](auto res_tag, auto zm_tag, auto os1_tag, auto full_tag) {
     constexpr bool RES = decltype(res_tag)::value;
     constexpr int ZM = decltype(zm_tag)::value;
+    constexpr bool OS1 = decltype(os1_tag)::value;
+    constexpr bool FULL = decltype(full_tag)::value;
+    static_assert(FULL || !OS1, "");
     const int Cout = a.Cout;
     const int Tout = a.Tout;
     constexpr unsigned YES = PlaneT<YB>::ES;
@@ -585,8 +589,8 @@ __global__ __launch_bounds__(512) void conv1d_wino8_kernel(Conv1dArgs a) {
     float vmax = 0.f;
     if constexpr (D == 1) {
       const int t = t0 + 4 * (nk * 32 + l32);
-      const int nvalid = Tout - t < 4 ? (Tout - t > 0 ? Tout - t : 0) : 4;
-      const bool full = nvalid == 4 && (Tout & 3) == 0;
+      const int nvalid = FULL ? 4 : (Tout - t < 4 ? (Tout - t > 0 ? Tout - t : 0) : 4);
+      const bool full = FULL || (nvalid == 4 && (Tout & 3) == 0);
       // gather GR vectors (residual, MRF sum) before computing and storing them: all 16 at once
       // pay one memory latency per tile instead of two (the accumulators are dead by now); with
       // both a residual and an MRF sum to read, 16 at once would spill, so two rounds of 8
@@ -608,8 +612,9 @@ __global__ __launch_bounds__(512) void conv1d_wino8_kernel(Conv1dArgs a) {
         for (int k = 0; k < GR; ++k) {
           const int r = r0 + k;
           const f32x4 yv = {y[0][r], y[1][r], y[2][r], y[3][r]};
-          const f32x4 v = wino_apply<RES, ZM, H3>(yv, bias[k], oslope, zdiv, gin[k], nvalid, vmax, sc);
+          const f32x4 v = wino_apply<RES, ZM, H3, OS1>(yv, bias[k], oslope, zdiv, gin[k], nvalid, vmax, sc);
           wino_store<YB>(rout, v, voff[k], full, nvalid);
+          if (r == 0) WSTAMP(23);
         }
       }
     } else {
@@ -620,8 +625,10 @@ __global__ __launch_bounds__(512) void conv1d_wino8_kernel(Conv1dArgs a) {
       const int tl = 4 * lane;
       const int t = t0 + tl;
       const int lim = (C::TW < Tout - t0 ? C::TW : Tout - t0) - tl;
+      // FULL: the lanes past the tile (tl >= TW) have nvalid 0 and an out-of-range offset: their
+      // 16-byte loads return 0 and their stores are dropped
       const int nvalid = lim < 4 ? (lim > 0 ? lim : 0) : 4;
-      const bool full = nvalid == 4 && (Tout & 3) == 0;
+      const bool full = FULL || (nvalid == 4 && (Tout & 3) == 0);
 #pragma unroll
       for (int ps = 0; ps < 2; ++ps) {
         if (jj < C::J) {
@@ -646,10 +653,11 @@ __global__ __launch_bounds__(512) void conv1d_wino8_kernel(Conv1dArgs a) {
 #pragma unroll
         for (int rr = 0; rr < 8; ++rr) {
           const f32x4 yv = *reinterpret_cast<const f32x4*>(tile + (grp * 8 + rr) * C::PITCH + tl);
-          const f32x4 v = wino_apply<RES, ZM, H3>(yv, bias[rr], oslope, zdiv, gin[rr], nvalid, vmax, sc);
+          const f32x4 v = wino_apply<RES, ZM, H3, OS1>(yv, bias[rr], oslope, zdiv, gin[rr], nvalid, vmax, sc);
           wino_store<YB>(rout, v, voff[rr], full, nvalid);
+          if (ps == 0 && rr == 0) WSTAMP(23);
         }
-        lds_sync();
+        if (ps == 0) lds_sync();  // the second pass overwrites the rows
       }
     }
     if (H3 && a.amax_out) publish_amax(a.amax_out, b, vmax);
@@ -660,14 +668,22 @@ __global__ __launch_bounds__(512) void conv1d_wino8_kernel(Conv1dArgs a) {
   using Z0 = std::integral_constant<int, 0>;
   using Z2 = std::integral_constant<int, 2>;
   using Z3 = std::integral_constant<int, 3>;
+  // workgroup-uniform (scalar) choices, once per wave
+  const bool wgfull = (a.Tout & 3) == 0 && t0 + C::TW <= a.Tout;
+  const bool os1 = a.out_slope == 1.f;
+  auto finish_rz = [&](auto res_tag, auto zm_tag) {
+    if (!wgfull) finish(res_tag, zm_tag, BF{}, BF{});
+    else if (os1) finish(res_tag, zm_tag, BT{}, BT{});
+    else finish(res_tag, zm_tag, BF{}, BT{});
+  };
   if (a.res) {
-    if (zm == 0) finish(BT{}, Z0{});
-    else if (zm == 2) finish(BT{}, Z2{});
-    else finish(BT{}, Z3{});
+    if (zm == 0) finish_rz(BT{}, Z0{});
+    else if (zm == 2) finish_rz(BT{}, Z2{});
+    else finish_rz(BT{}, Z3{});
   } else {
-    if (zm == 0) finish(BF{}, Z0{});
-    else if (zm == 2) finish(BF{}, Z2{});
-    else finish(BF{}, Z3{});
+    if (zm == 0) finish_rz(BF{}, Z0{});
+    else if (zm == 2) finish_rz(BF{}, Z2{});
+    else finish_rz(BF{}, Z3{});
   }
 }
 

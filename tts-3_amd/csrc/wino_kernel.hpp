@@ -129,14 +129,16 @@ __device__ __forceinline__ WinoIn wino_gather(const rsrc_t& rres, const rsrc_t& 
   return g;
 }
 
-template <bool RES, int ZM, bool H3>
+// OS1: the caller knows oslope == 1 (lrelu2(x, 1) = max(x, x) = x, the same bits)
+template <bool RES, int ZM, bool H3, bool OS1 = false>
 __device__ __forceinline__ f32x4 wino_apply(f32x4 y, float bias, float oslope, float zdiv, const WinoIn& g, int nvalid,
                                              float& vm, float sc = 1.f) {
   f32x4 v;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     // sc: the f16x3 rescale (an exact power of two), so fma(y, sc, bias) rounds like (y * sc) + bias
-    float x = lrelu2(fmaf(y[j], sc, bias), oslope);
+    float x = fmaf(y[j], sc, bias);
+    if (!OS1) x = lrelu2(x, oslope);
     if (RES) x = x + g.rv[j];
     if (ZM == 2) x = g.zv[j] + x;
     if (ZM == 3) x = (g.zv[j] + x) / zdiv;
